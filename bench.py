@@ -2,12 +2,13 @@
 """bench.py -- throughput of the DH-AUG hot path on MI355X.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload fwd|fk_gen_fwd|gan_step|video|fk] [--batch 65536]
+                    [--dump-outputs DIR] [--full]
 
 One "step" = one pass of the hot path over one batch of synthetic input that is already resident in HBM:
     fwd        (default) FK + Gen + D3 + D2 forward, B = 65 536 poses per GPU, D = 256, fp32 FK
-               (north_star's target workload; superset of BASELINE.json configs[1]).  Timed in BOTH arithmetics of the dense
-               layers: `value` = bf16 (one MFMA pass), `value_parity` = f16x3 (fp16 hi+lo operands, three MFMA terms --
-               the mode that meets the 1e-4 logit tolerance against the fp32 reference, tests/test_gpu_models.py)
+               (north_star's target workload; superset of BASELINE.json configs[1]).  `value` = bf16 (one MFMA pass); with
+               --full also `value_parity` = f16x3 (fp16 hi+lo operands, three MFMA terms -- the mode that meets the 1e-4 logit
+               tolerance against the fp32 reference, tests/test_gpu_models.py)
     fk_gen_fwd FK + Gen forward only (configs[1] exactly)
     gan_step   full single-frame GAN iteration (configs[2]/[3]): 2+2 WGAN-GP critic steps (flip copies), G step every
                5th iteration, fused Adam; with N > 1 one RCCL all-reduce per optimizer step
@@ -17,6 +18,13 @@ N > 1: one process per GPU.  Launched by torch.distributed.run (RANK / WORLD_SIZ
 launched plainly with --gpus N it starts the N ranks itself, before touching the GPU.  The batch shards across ranks
 (B per rank, weak scaling); the forward workloads have no exchange step, the training workloads all-reduce the flat
 gradient bucket of the network being stepped.  Rank 0 prints ONE JSON line.
+
+A plain run sets up, pre-warms, runs W warm-up steps, times ONE block of exactly K steps (`ms_per_step`, `value`), writes the
+outputs if --dump-outputs is given and prints the line.  --full adds what takes runs of its own: five timed blocks (median),
+the forward in the other arithmetic, the other workloads and DenseDim 1000 (`extra`), the per-kernel rooflines, the CPU
+baselines and, with several ranks, the all-reduce timed alone.
+--dump-outputs DIR: rank 0 writes what the last timed step computed, as float32 DIR/<name>.npy (fwd: the fake world poses and
+both critics' logits; fk_gen_fwd: the fake poses; fk: the joints; gan_step / video: the weights of every network after it).
 """
 import argparse
 import json
@@ -148,6 +156,24 @@ def event_time(fn, iters, warm, rewarm_s=0.3):
     return s.elapsed_time(e) * 1e-3 / iters
 
 
+def dump_outputs(path, arrays, limit_bytes=60 << 20):
+    """arrays (name -> tensor) as float32 <path>/<name>.npy.  If they hold more than limit_bytes in all (60 MiB: with the .npy
+    headers the files stay below 64 MB), each keeps the same share of its elements, at positions drawn from a CPU generator
+    seeded with 0: the same sample in every run of the same arguments."""
+    import numpy as np
+    import torch
+    os.makedirs(path, exist_ok=True)
+    total = sum(v.numel() for v in arrays.values())
+    keep = min(1.0, limit_bytes / 4.0 / max(1, total))
+    g = torch.Generator().manual_seed(0)
+    for name, v in sorted(arrays.items()):
+        v = v.detach().float()
+        if keep < 1.0:
+            idx = torch.randint(v.numel(), (int(v.numel() * keep),), generator=g).sort().values
+            v = v.reshape(-1)[idx.to(v.device)]
+        np.save(os.path.join(path, name + ".npy"), v.cpu().numpy())
+
+
 def dist_info(dist, torch, backend, world, local, device_name):
     """what the exchange ran on: backend, world size, the collective library's version and every rank's device -- so that the
     driver can see that RCCL ("nccl" on ROCm) saw N ranks on N devices.  Never raises."""
@@ -204,9 +230,15 @@ def parse(argv=None):
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--reps", type=int, default=5,
+    ap.add_argument("--reps", type=int, default=None,
                     help="the block of --steps timed steps is repeated this many times (after ONE warm-up): `value` / `ms_per_step` "
-                         "are the MEDIAN block's, value_min / value_max the slowest / fastest block's")
+                         "are the MEDIAN block's, value_min / value_max the slowest / fastest block's (default 1; 5 with --full)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: five timed blocks, the other arithmetic, extra workloads, "
+                         "rooflines, CPU baselines, the all-reduce alone (the --no-* switches below thin this out)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float32; at most 64 MB in all, a fixed "
+                         "seeded sample of larger outputs)")
     ap.add_argument("--prewarm", type=float, default=1.0,
                     help="seconds of the workload run before the W warmup steps, untimed: MI355X clocks take a few hundred ms "
                          "of load to leave their idle state (the same step measures 0.28 ms right after start-up, 0.25 ms warm)")
@@ -225,7 +257,12 @@ def parse(argv=None):
     ap.add_argument("--dry-run", action="store_true",
                     help="rendezvous only: every rank joins the process group, the timing exchange runs, rank 0 prints the line "
                          "(no GPU work; with DHAUG_DIST_BACKEND=gloo this rehearses the N-rank launch path on a CPU box)")
-    return ap.parse_args(argv)
+    a = ap.parse_args(argv)
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    if a.reps is None:
+        a.reps = 5 if a.full else 1
+    return a
 
 
 def main():
@@ -340,19 +377,20 @@ def main():
         for m in (G, D3, D2):
             m.precision = p
 
+    # each step returns what a caller of it receives, by name (--dump-outputs); the training steps' result is the weights
     def step_fk():
-        ops.fk_forward(ang, bl, root)
+        return {"fk_joints": ops.fk_forward(ang, bl, root)}
 
     def step_fk_gen():
         with torch.no_grad():
-            return G(z)
+            return {"fake_poses": G(z)}
 
     def step_fwd():
         with torch.no_grad():
             bf = G.precision == "bf16"
             fw, xc, kcs, p2 = G.sample_for_critics(z, (quat, trans, cam9), inputs_bf16=bf)   # FK tail + critic inputs, one launch
             l3, l2 = score_fake_pair(D3, D2, xc, kcs, p2)                                    # both critics, one launch
-        return l3, l2
+        return {"fake_world_poses": fw, "logits_d3d": l3, "logits_d2d": l2}
 
     # one rank: the iteration is one hipGraph; several ranks: graph segments with the all-reduces between them
     # (graphs.SegmentedCall).  --graph off: eager
@@ -386,7 +424,12 @@ def main():
 
     steps = {"fk": step_fk, "fk_gen_fwd": step_fk_gen, "fwd": step_fwd, "gan_step": step_gan, "video": step_video}
 
+    last = {}                                    # what the last step of the last timed block returned (--dump-outputs)
+
     def timed(fn, k, w):
+        # the device generator restarts here, so the random draws of the block's steps (generator jitter, training noise) do
+        # not depend on how many steps the clock-driven pre-warm ran: with the same arguments the last step sees the same inputs
+        torch.cuda.manual_seed(1234 + rank)
         for _ in range(w):
             fn()
         torch.cuda.synchronize()
@@ -395,8 +438,9 @@ def main():
         torch.cuda.synchronize()
         c0 = _lib.CALLS[0]
         t0 = time.perf_counter()
-        for _ in range(k):
+        for _ in range(k - 1):
             fn()
+        last["out"] = fn()
         torch.cuda.synchronize()
         if world > 1:
             dist.barrier()
@@ -421,8 +465,9 @@ def main():
     def prewarm(fn, training):
         if a.prewarm <= 0:
             return
-        if world > 1 and training:
-            # a training step holds a collective: every rank must run the same number of them, so the pre-warm is a step
+        if training:
+            # a training step holds a collective: every rank must run the same number of them; and it moves the weights the
+            # timed steps start from, which must not depend on the host's speed (--dump-outputs).  So the pre-warm is a step
             # count here (~prewarm seconds at the single-GPU rates), not a wall-clock loop
             for _ in range(max(1, int(a.prewarm * 80))):
                 fn()
@@ -496,6 +541,9 @@ def main():
         graph_calibration = {"graph_ms": cal["graph"], "eager_ms": cal["eager"], "picked": "graph" if mode["graph"] else "eager"}
         it[0] = 0
     t, calls, blocks = timed_reps(steps[a.workload], a.steps, a.warmup, a.reps)
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, {"params_" + k[len("optimizer_"):]: v.flat_param for k, v in models.items()
+                                      if k.startswith("optimizer")} if training else last["out"])
     value = N * world * a.steps / t
     out = {"metric": "augmented poses/sec (FK+GAN step), 16-joint batch=65536", "value": value, "unit": "poses/s",
            "n_gpus": world, "steps": a.steps, "warmup": a.warmup, "prewarm_s": a.prewarm, "ms_per_step": t / a.steps * 1e3,
@@ -512,7 +560,7 @@ def main():
            "ms_per_step_min": blocks[0] / a.steps * 1e3, "ms_per_step_max": blocks[-1] / a.steps * 1e3}
 
     # the forward workload in the OTHER arithmetic, same inputs (bf16 <-> parity), with its own step time
-    if fwd_like:
+    if fwd_like and a.full:
         other = "bf16" if main_prec == "f16x3" else "f16x3"
         set_precision(other)
         k = max(5, a.steps // 2)
@@ -529,7 +577,7 @@ def main():
         out["dist"] = dist_info(dist, torch, backend, world, local, torch.cuda.get_device_name(local))
     if training and world > 1:
         out["allreduce_bytes_per_optimizer_step"] = bucket_bytes
-    if world > 1:
+    if world > 1 and a.full:
         # the exchange step of the training path, timed alone: all-reduce of the flat gradient buckets (D2 / G / D3 at D = 256,
         # and a DenseDim-1000 motion critic's) over the job's backend ("nccl" = RCCL over xGMI).  Never fails the bench line.
         try:
@@ -556,7 +604,7 @@ def main():
             out["allreduce_alone"] = {"error": repr(ex)}
 
     extra = {}
-    if not a.no_extra and not video:
+    if a.full and not a.no_extra and not video:
         set_precision("bf16")
         for name in ("fk_gen_fwd", "fwd", "gan_step"):
             if name != a.workload:
@@ -638,7 +686,7 @@ def main():
                 del m1k, g1k, d31k, d21k
             except Exception as ex:
                 extra["fwd_D1000_error"] = repr(ex)[:200]
-    if not a.no_extra and not video and world == 1 and a.workload == "fwd":
+    if a.full and not a.no_extra and not video and world == 1 and a.workload == "fwd":
         # the video iteration at BASELINE.json configs[4]'s per-GPU shape (B = 512 clips x R = 9 frames, DenseDim 1000, the two
         # frame critics + the two motion critics, G step every fifth iteration): eager and as hipGraphs, ten iterations each
         # (two G steps), so that the driver's default line carries it
@@ -767,7 +815,7 @@ def main():
             comm = 2 * per_opt.get("d3d", 0.0) + 2 * per_opt.get("d2d", 0.0) + 0.2 * per_opt.get("G", 0.0)
             out["allreduce_share_of_gan_step_upper_bound"] = comm * 1e-3 / extra["gan_step_ms_per_step"]
 
-    if rank == 0 and not a.no_roofline and not video:
+    if rank == 0 and a.full and not a.no_roofline and not video:
         from dhaug_amd import fused
         set_precision("bf16")
         x3 = torch.randn(B, 48, device=dev) * 0.3
@@ -818,7 +866,7 @@ def main():
 
     if rank == 0:
         cpu = None
-        if world == 1 and not a.no_cpu_baseline:
+        if world == 1 and a.full and not a.no_cpu_baseline:
             sd = lambda m: {k: v.detach().cpu() for k, v in m.state_dict().items()}
             if video:
                 cpu = cpu_baseline_video(D, R, sd(G), sd(D3), sd(D2), sd(models["model_motion_d3d"]), sd(models["model_motion_d2d"]),

@@ -9,7 +9,7 @@ ONLY=${2:-all}                      # optional: the workloads to (re)collect, e.
 want() { { [ "$ONLY" = all ] && [ "$1" != step_parity ] && [ "$1" != fwd_d1000 ] && [ "$1" != fwd_d1000_parity ]; } || [[ " $ONLY " == *" $1 "* ]]; }
 O=gpurun_out/profiles
 mkdir -p $O
-B="python bench.py --no-cpu-baseline --no-extra --no-roofline --prewarm 0 --reps 1"
+B="python bench.py --full --no-cpu-baseline --no-extra --no-roofline --prewarm 0 --reps 1"   # (--full: the forward's other arithmetic too)
 stats() {  # name, args...
   local name=$1; shift
   timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/prof_$name -o r -- "$@" > gpurun_out/prof_$name.log 2>&1 || return 1
