@@ -1,4 +1,16 @@
-"""Only the piece of R/models_Fk_GAN/video_mode_operate.py that the hot path reads."""
+"""The pieces of R/models_Fk_GAN/video_mode_operate.py that the video GAN epoch reads: the receptive field, and the
+real-clip loader of the multi-frame mode (GAN_video_ChunkedGenerator :35-192, video_mode_random_bl_aug :879-896,
+video_mode_dataloader_update :898-968) kept on the device.
+
+The loader's sequences sit concatenated in device memory; every batch is one dhaug_clip_gather launch over a slice of the
+epoch's permuted record table (uploaded once per epoch), so there is no host work per clip and no host <-> device copy per
+batch.  Batches are device fp32 tensors; they equal the reference's float64 numpy batches cast to fp32 bit for bit (the
+gather only copies, negates and permutes)."""
+import numpy as np
+import torch
+
+from .. import ops
+from ..function_aug.dataloader_update import BL_TEMPLATES
 
 
 def video_receptive_field(filter_widths):
@@ -13,3 +25,248 @@ def frames_from_args(args):
     if getattr(args, "single_or_multi_train_mode", "single") == "multi":
         return video_receptive_field([int(x) for x in args.architecture.split(",")])
     return 1
+
+
+# left / right joints of the 16-joint H36M skeleton, for the 2D keypoints and the 3D joints alike (:940-943)
+JOINTS_LEFT = [4, 5, 6, 10, 11, 12]
+JOINTS_RIGHT = [1, 2, 3, 13, 14, 15]
+
+
+def _int(v, name, lo):
+    if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)) or v < lo:
+        raise ValueError("%s must be an integer >= %d, got %r" % (name, lo, v))
+    return int(v)
+
+
+def _flip_perm(left, right, name):
+    """joint permutation of a flip: out[left] = in[right], out[right] = in[left]; the lists must be a disjoint pair"""
+    if left is None or right is None:
+        raise ValueError("augment=True needs %s_left and %s_right" % (name, name))
+    left, right = [int(j) for j in left], [int(j) for j in right]
+    both = left + right
+    if len(left) != len(right) or len(set(both)) != len(both) or any(j < 0 or j >= 16 for j in both):
+        raise ValueError("%s_left / %s_right must be two disjoint lists of equal length over joints 0..15: %r %r"
+                         % (name, name, left, right))
+    perm = list(range(16))
+    for a, b in zip(left, right):
+        perm[a], perm[b] = b, a
+    return perm
+
+
+class GAN_video_ChunkedGenerator:
+    """Drop-in for GAN_video_ChunkedGenerator (R/models_Fk_GAN/video_mode_operate.py:35-192).
+
+    Same signature, pair list, shuffle stream (np.random.RandomState(random_seed)), batch split and endless / state
+    resume as the reference.  Differences: next_epoch() yields (cam, poses_3d, poses_2d) as DEVICE fp32 tensors (None where
+    the reference yields None), freshly allocated per batch; next_pairs() returns the pairs as an (P, 4) int64 array also
+    without shuffle.  Poses are 16 joints: (frames, 16, 3) and (frames, 16, 2) per sequence, cameras one vector each.  The
+    lists are concatenated once here and uploaded to the current device at the first next_epoch()."""
+
+    def __init__(self, batch_size, cameras, poses_3d, poses_2d, chunk_length, pad=0, causal_shift=0, shuffle=True,
+                 random_seed=1234, augment=False, kps_left=None, kps_right=None, joints_left=None, joints_right=None,
+                 endless=False):
+        if poses_2d is None or len(poses_2d) == 0:
+            raise ValueError("poses_2d must be a non-empty list of (frames, 16, 2) arrays")
+        S = len(poses_2d)
+        if poses_3d is not None and len(poses_3d) != S:
+            raise ValueError("poses_3d and poses_2d differ in length: %d vs %d" % (len(poses_3d), S))
+        if cameras is not None and len(cameras) != S:
+            raise ValueError("cameras and poses_2d differ in length: %d vs %d" % (len(cameras), S))
+        p2 = [np.asarray(p) for p in poses_2d]
+        lengths = np.array([p.shape[0] for p in p2], dtype=np.int64)
+        for i, p in enumerate(p2):
+            if p.shape[1:] != (16, 2):
+                raise ValueError("poses_2d[%d] has shape %s, expected (frames, 16, 2)" % (i, p.shape))
+        p3 = None
+        if poses_3d is not None:
+            p3 = [np.asarray(p) for p in poses_3d]
+            for i, p in enumerate(p3):
+                if p.shape != (lengths[i], 16, 3):
+                    raise ValueError("poses_3d[%d] has shape %s, expected (%d, 16, 3)" % (i, p.shape, lengths[i]))
+        cam = None
+        if cameras is not None:
+            cam = [np.asarray(c).reshape(-1) for c in cameras]
+            if len({c.shape[0] for c in cam}) != 1:
+                raise ValueError("cameras differ in width")
+        self._setup(batch_size, lengths, None if cam is None else cam[0].shape[0], p3 is not None, chunk_length, pad,
+                    causal_shift, shuffle, random_seed, augment, kps_left, kps_right, joints_left, joints_right, endless)
+        # one concatenation per construction; the upload follows at the first next_epoch()
+        cat = lambda xs, w: np.concatenate([x.reshape(-1, 16, w) for x in xs]).astype(np.float32, copy=False)
+        self._host = (None if cam is None else np.stack(cam).astype(np.float32, copy=False),
+                      None if p3 is None else cat(p3, 3), cat(p2, 2))
+        self._dev = None
+
+    @classmethod
+    def _from_device(cls, batch_size, cams, seq3d, seq2d, lengths, chunk_length, **kw):
+        """the same loader over sequences already concatenated on the device: cams (S, cam_w) or None, seq3d (T,16,3) or
+        None, seq2d (T,16,2) fp32 device tensors, lengths (S,) host integers summing to T; keyword arguments as __init__"""
+        self = cls.__new__(cls)
+        lengths = np.asarray(lengths, dtype=np.int64).reshape(-1)
+        T = int(lengths.sum())
+        if (lengths < 0).any() or tuple(seq2d.shape) != (T, 16, 2) or (seq3d is not None and tuple(seq3d.shape) != (T, 16, 3)):
+            raise ValueError("device sequences do not match the lengths")
+        if cams is not None and (cams.dim() != 2 or cams.shape[0] != lengths.shape[0]):
+            raise ValueError("cams must be (sequences, cam_w)")
+        self._setup(batch_size, lengths, None if cams is None else cams.shape[1], seq3d is not None, chunk_length, **kw)
+        self._host = None
+        self._put(cams, seq3d, seq2d)
+        return self
+
+    def _setup(self, batch_size, lengths, cam_w, has3d, chunk_length, pad=0, causal_shift=0, shuffle=True,
+               random_seed=1234, augment=False, kps_left=None, kps_right=None, joints_left=None, joints_right=None,
+               endless=False):
+        batch_size = _int(batch_size, "batch_size", 1)
+        cl = _int(chunk_length, "chunk_length", 1)
+        pad = _int(pad, "pad", 0)
+        causal_shift = _int(causal_shift, "causal_shift", -(1 << 29))
+        if pad >= (1 << 29) or causal_shift >= (1 << 29):
+            raise ValueError("pad / causal_shift out of range")
+        if int(lengths.sum()) >= (1 << 31) - 2 * cl:
+            raise ValueError("the sequences hold %d frames; at most 2^31 are supported" % int(lengths.sum()))
+        self._perm2d = self._perm3d = None
+        if augment:
+            self._perm2d = _flip_perm(kps_left, kps_right, "kps")
+            if has3d:
+                self._perm3d = _flip_perm(joints_left, joints_right, "joints")
+            if cam_w is not None and cam_w < 8:
+                raise ValueError("augment flips camera columns 2 and 7: cameras need >= 8 columns, got %d" % cam_w)
+        # the pair list: per sequence its chunks [start, end), centred on the sequence, then (augment) the same flipped
+        n = (lengths + cl - 1) // cl
+        off = (n * cl - lengths) // 2
+        reps = n * (2 if augment else 1)
+        P = int(reps.sum())
+        seq = np.repeat(np.arange(len(lengths), dtype=np.int64), reps)
+        m = np.arange(P, dtype=np.int64) - np.repeat(np.cumsum(reps) - reps, reps)
+        nn = np.repeat(n, reps)
+        start = (m % np.maximum(nn, 1)) * cl - np.repeat(off, reps)
+        self._pair_arr = np.stack([seq, start, start + cl, (m >= nn).astype(np.int64)], axis=1).reshape(P, 4)
+        self._pairs = None
+        self._lengths = lengths
+        self._cam_w, self._has3d = cam_w, has3d
+        self.frames = cl + 2 * pad
+        self.num_batches = (P + batch_size - 1) // batch_size
+        self.batch_size = batch_size
+        self.random = np.random.RandomState(random_seed)
+        self.shuffle = shuffle
+        self.pad = pad
+        self.causal_shift = causal_shift
+        self.endless = endless
+        self.state = None
+        self.augment = augment
+        self.kps_left, self.kps_right, self.joints_left, self.joints_right = kps_left, kps_right, joints_left, joints_right
+        self._records = (None, None)
+
+    def _put(self, cams, seq3d, seq2d):
+        dev = seq2d.device
+        starts = np.concatenate([[0], np.cumsum(self._lengths)[:-1]]).astype(np.int64)
+        self._dev = dict(cams=cams, seq3d=seq3d, seq2d=seq2d,
+                         offset=torch.from_numpy(starts).to(dev),
+                         length=torch.from_numpy(self._lengths.astype(np.int32)).to(dev))
+
+    def _device_data(self):
+        if self._dev is None:
+            dev = torch.device("cuda", torch.cuda.current_device())
+            up = lambda a: None if a is None else torch.from_numpy(a).to(dev)
+            cams, seq3d, seq2d = self._host
+            self._put(up(cams), up(seq3d), up(seq2d))
+            self._host = None
+        return self._dev
+
+    @property
+    def pairs(self):
+        """the reference's pair list: (seq_idx, start_frame, end_frame, flip) tuples"""
+        if self._pairs is None:
+            self._pairs = [(int(s), int(a), int(b), bool(f)) for s, a, b, f in self._pair_arr]
+        return self._pairs
+
+    def num_frames(self):
+        return self.num_batches * self.batch_size
+
+    def random_state(self):
+        return self.random
+
+    def set_random_state(self, random):
+        self.random = random
+
+    def augment_enabled(self):
+        return self.augment
+
+    def next_pairs(self):
+        if self.state is None:
+            # RandomState.permutation(P) draws the order the reference's permutation(pairs) does
+            pairs = self._pair_arr[self.random.permutation(len(self._pair_arr))] if self.shuffle else self._pair_arr
+            return 0, pairs
+        return self.state
+
+    def _device_records(self, pairs, dev):
+        """pairs (P, 4) -> int32 device table, uploaded once per epoch (kept while the same array comes back on resume)"""
+        if self._records[0] is not pairs:
+            self._records = (pairs, torch.from_numpy(np.ascontiguousarray(pairs, dtype=np.int32)).to(dev))
+        return self._records[1]
+
+    def next_epoch(self):
+        d = self._device_data()
+        B = self.batch_size
+        while True:
+            start_idx, pairs = self.next_pairs()
+            rec = self._device_records(pairs, d["seq2d"].device)
+            for b in range(start_idx, self.num_batches):
+                cam, p3, p2 = ops.clip_gather(d["seq3d"], d["seq2d"], d["cams"], d["offset"], d["length"],
+                                              rec[b * B:(b + 1) * B], self.frames, self.pad, self.causal_shift,
+                                              self._perm3d, self._perm2d)
+                if self.endless:
+                    self.state = (b + 1, pairs)
+                yield cam, p3, p2
+            if not self.endless:
+                return
+            self.state = None
+
+
+def video_mode_random_bl_aug(x, template_idx=None):
+    """Drop-in for video_mode_random_bl_aug (:879-896): x (N,16,3), one sequence -> every frame's bones keep their directions
+    and take the lengths of ONE template (drawn with np.random.choice(5, 1) as at :888, or given)."""
+    if template_idx is None:
+        template_idx = np.random.choice(BL_TEMPLATES.shape[0], 1)
+    k = int(np.asarray(template_idx).reshape(-1)[0])
+    x = x.reshape(-1, 16, 3)
+    lens = torch.as_tensor(BL_TEMPLATES[k], device=x.device).expand(x.shape[0], 15)
+    return ops.bone_length_swap(x, lens)
+
+
+def video_mode_dataloader_update(args, data_dict, device):
+    """Drop-in for video_mode_dataloader_update (:898-968): bone-length swap of every training sequence (one template per
+    sequence) and re-projection with the sequence's camera, then data_dict['target_GAN_loader'] over the results.
+
+    The whole epoch is one upload of the raw sequences, one dhaug_bone_length_swap and one dhaug_project_to_2d launch over
+    all frames (per-row template and camera rows); nothing is copied back.  The template draws stay on the host, one
+    np.random.choice per sequence in sequence order, so the global numpy stream advances as in the reference.  As in the
+    reference, the loader is built with the default seed 1234 every epoch, so every epoch sees the same clip order."""
+    poses, cams = data_dict['poses_train'], data_dict['cams_train']
+    S = len(poses)
+    for key in ('poses_train_2d', 'actions_train', 'cams_train'):
+        if len(data_dict[key]) != S:
+            raise ValueError("data_dict['%s'] has %d entries, poses_train %d" % (key, len(data_dict[key]), S))
+    if S == 0:
+        raise ValueError("data_dict['poses_train'] is empty")
+    lengths = np.array([np.shape(p)[0] for p in poses], dtype=np.int64)
+    for i, p in enumerate(poses):
+        if np.shape(p)[1:] != (16, 3):
+            raise ValueError("poses_train[%d] has shape %s, expected (frames, 16, 3)" % (i, np.shape(p)))
+    cam = [np.asarray(c, dtype=np.float32).reshape(-1) for c in cams]
+    if len({c.shape[0] for c in cam}) != 1 or cam[0].shape[0] < 9:
+        raise ValueError("cams_train must be vectors of one width >= 9")
+    R = video_receptive_field([int(w) for w in args.architecture.split(',')])
+    tmpl = np.array([np.random.choice(BL_TEMPLATES.shape[0], 1)[0] for _ in range(S)], dtype=np.int64)
+
+    T = int(lengths.sum())
+    x = torch.from_numpy(np.concatenate([np.asarray(p, dtype=np.float32) for p in poses])).to(device)
+    cam = torch.from_numpy(np.stack(cam)).to(device)
+    seq_of_row = torch.repeat_interleave(torch.arange(S, device=device), torch.from_numpy(lengths).to(device),
+                                         output_size=T)
+    row_tmpl = torch.from_numpy(tmpl).to(device)[seq_of_row]
+    p3 = ops.bone_length_swap(x, torch.as_tensor(BL_TEMPLATES, device=device)[row_tmpl])
+    p2 = ops.project_to_2d(p3, cam[:, :9][seq_of_row])
+    data_dict['target_GAN_loader'] = GAN_video_ChunkedGenerator._from_device(
+        args.batch_size // 1, cam, p3, p2, lengths, chunk_length=1, pad=(R - 1) // 2, causal_shift=0, shuffle=True,
+        augment=False, kps_left=JOINTS_LEFT, kps_right=JOINTS_RIGHT, joints_left=JOINTS_LEFT, joints_right=JOINTS_RIGHT)
+    return

@@ -214,6 +214,36 @@ def project_to_2d(cam3d, cam9):
     return out
 
 
+def clip_gather(seq3d, seq2d, cams, seq_offset, seq_len, records, frames, pad, causal_shift=0, perm3d=None, perm2d=None,
+                out3d=None, out2d=None, out_cam=None):
+    """clips of the video loader (dhaug_clip_gather): seq3d (T,16,3) or None, seq2d (T,16,2), cams (S,cam_w) or None,
+    seq_offset (S,) int64, seq_len (S,) int32, records (nrec,4) int32 -> (out_cam, out3d, out2d) as (nrec, cam_w),
+    (nrec, frames, 16, 3), (nrec, frames, 16, 2); None where the input is None.  perm3d / perm2d: host sequences of 16
+    joint indices (None = identity).  out*: optional preallocated outputs of those shapes."""
+    s2 = _dev(seq2d, torch.float32, "clip_gather").reshape(-1, 32)
+    s3 = None if seq3d is None else _dev(seq3d, torch.float32, "clip_gather").reshape(-1, 48)
+    c = None if cams is None else _dev(cams, torch.float32, "clip_gather")
+    off = _dev(seq_offset, torch.int64, "clip_gather")
+    ln = _dev(seq_len, torch.int32, "clip_gather")
+    rec = _dev(records, torch.int32, "clip_gather").reshape(-1, 4)
+    n, dev = rec.shape[0], s2.device
+    cam_w = 0 if c is None else c.reshape(c.shape[0], -1).shape[1]
+
+    def out(t, shape):
+        if t is None:
+            return torch.empty(shape, dtype=torch.float32, device=dev)
+        assert t.dtype == torch.float32 and t.is_cuda and t.is_contiguous() and tuple(t.shape) == shape, "clip_gather output"
+        return t
+
+    o2 = out(out2d, (n, frames, 16, 2))
+    o3 = None if s3 is None else out(out3d, (n, frames, 16, 3))
+    oc = None if c is None else out(out_cam, (n, cam_w))
+    perm = lambda p: None if p is None else (ctypes.c_int8 * 16)(*[int(v) for v in p])
+    _lib.call("dhaug_clip_gather", _p(s3), _p(s2), _p(c), cam_w, _p(off), _p(ln), _p(rec), n, int(frames), int(pad),
+              int(causal_shift), perm(perm3d), perm(perm2d), _p(o3), _p(o2), _p(oc), _stream())
+    return oc, o3, o2
+
+
 def center_flip(x, center, flip, adjoint=False):
     C = x.shape[-1]
     v = _dev(x, torch.float32, "center_flip").reshape(-1, 16 * C)

@@ -172,6 +172,23 @@ int dhaug_center_flip(const float* in, float* out, int64_t N, int C, int center,
 int dhaug_center_flip_backward(const float* grad_out, float* grad_in, int64_t N, int C, int center, int flip,
                                void* stream);
 
+/* Clip gather of the video loader: GAN_video_ChunkedGenerator.next_epoch (R/models_Fk_GAN/video_mode_operate.py:126-183) for
+ * nrec records (seq, start, end, flip) taken from a device array: for record i and output frame f < frames = end - start + 2*pad,
+ *   src = seq_offset[seq] + clamp(start - pad - causal_shift + f, 0, seq_len[seq] - 1)   (== the slice + np.pad 'edge');
+ * flip: x -> -x and joint j <- joint perm[j] (perm3d for 3D, perm2d for 2D), camera columns 2 and 7 negated.
+ *   seq3d (total_frames,16,3), seq2d (total_frames,16,2): the sequences concatenated; cams (S, cam_w); seq_offset (S) int64 and
+ *   seq_len (S) int32: first row and length (>= 1) of each sequence; records (nrec,4) int32, every seq < S (not checked: the
+ *   caller builds them) -> out3d (nrec,frames,16,3), out2d (nrec,frames,16,2), out_cam (nrec,cam_w), every element written.
+ *   perm3d / perm2d: HOST arrays of 16 entries, read during the call; each a permutation of 0..15 (DHAUG_EINVAL otherwise),
+ *   NULL = identity.
+ * seq3d/out3d and cams/out_cam may be NULL together (the reference's poses_3d / cameras = None).  seq2d, seq3d, out2d, out3d
+ * and records 16-byte aligned (DHAUG_EALIGN); nrec * frames < 2^31 / 12 (DHAUG_EUNSUPPORTED).  Data movement only: the output
+ * is the reference's float64 batch cast to fp32, bit for bit. */
+int dhaug_clip_gather(const float* seq3d, const float* seq2d, const float* cams, int cam_w,
+                      const int64_t* seq_offset, const int32_t* seq_len, const int32_t* records, int64_t nrec,
+                      int frames, int pad, int causal_shift, const int8_t* perm3d, const int8_t* perm2d,
+                      float* out3d, float* out2d, float* out_cam, void* stream);
+
 /* ------------------------------------------------------------------------------------------------------
  * Dense layers: bf16 MFMA GEMM with fused epilogue
  * ---------------------------------------------------------------------------------------------------- */
