@@ -28,6 +28,7 @@ SIGNATURES = {
     "dhaug_center_flip": [_vp, _vp, _i64, _i32, _i32, _i32, _vp],
     "dhaug_center_flip_backward": [_vp, _vp, _i64, _i32, _i32, _i32, _vp],
     "dhaug_clip_gather": [_vp, _vp, _vp, _i32, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp],
+    "dhaug_pose_metrics": [_vp, _vp, _i64, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp],
     "dhaug_gemm_bf16_dmask": [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _i32, _f32, _vp, _i64, _i64, _i64, _i64, _vp],
     "dhaug_gemm_bf16_dmask_pad": [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _i32, _f32, _vp, _i64, _i64, _i64, _i64, _i64, _vp],
     "dhaug_gemm_bf16_dbits": [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _i32, _f32, _vp, _i64, _i64, _vp],
@@ -138,6 +139,11 @@ SIGNATURES["dhaug_mlp_forward"] = [ctypes.POINTER(MlpUnit), _i32, _i64, _vp]
 SIGNATURES["dhaug_pack_wfrag_f16x2"] = [_vp, _i64, _vp, _i64, _i64, _i64, _vp]
 SIGNATURES["dhaug_pack_wfrag_f16x2_t16"] = [_vp, _i64, _vp, _i64, _i64, _i64, _vp]
 SIGNATURES["dhaug_mlp_forward_x3"] = [ctypes.POINTER(MlpUnit), _i32, _i64, _vp]
+
+EVAL_MAX_THRESHOLDS = 32
+EVAL_MAX_MULTIPLICITY = 1024
+EVAL_TOTALS_WORDS = 3 + EVAL_MAX_THRESHOLDS            # struct dhaug_eval_totals as int64 words
+EVAL_WORKSPACE_BYTES = 2048 * EVAL_TOTALS_WORDS * 8
 
 ERRORS = {-1: "DHAUG_EINVAL (bad argument)", -2: "DHAUG_EALIGN (alignment contract violated)",
           -3: "DHAUG_EUNSUPPORTED (shape not implemented)"}

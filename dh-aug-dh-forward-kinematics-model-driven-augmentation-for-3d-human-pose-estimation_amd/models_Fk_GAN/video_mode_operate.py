@@ -270,3 +270,56 @@ def video_mode_dataloader_update(args, data_dict, device):
         args.batch_size // 1, cam, p3, p2, lengths, chunk_length=1, pad=(R - 1) // 2, causal_shift=0, shuffle=True,
         augment=False, kps_left=JOINTS_LEFT, kps_right=JOINTS_RIGHT, joints_left=JOINTS_LEFT, joints_right=JOINTS_RIGHT)
     return
+
+
+def _upload_batch(b, device):
+    """a next_epoch() batch -> device fp32: numpy (the reference's ChunkedGenerator) through pinned memory, tensors as they are"""
+    if torch.is_tensor(b):
+        return b.to(device=device, dtype=torch.float32, non_blocking=True)
+    t = torch.from_numpy(np.ascontiguousarray(b, dtype=np.float32))
+    return t.pin_memory().to(device, non_blocking=True)
+
+
+def video_mode_evaluate(args, data_loader, model_pos_eval, device, summary=None,
+                        writer=None, key='', tag='', flipaug='', get_pck_auc=False):
+    """Drop-in for video_mode_evaluate (R/models_Fk_GAN/video_mode_operate.py:769-859): the reference's reshapes, posenet calls
+    and flip (dhaug_center_flip per frame); the metrics are summed on the device and read once, at the end (see
+    function_aug/model_pos_eval.py).  Returns (p1 mm, p2 mm, pck %, auc %)."""
+    from ..function_aug.model_pos_eval import finish, flip_pose, write_scalars
+    from ..utils.loss import PoseMetricsAccumulator
+
+    receptive_field = video_receptive_field([int(x) for x in args.architecture.split(',')])
+    model_pos_eval.eval()
+    acc = PoseMetricsAccumulator(device, center=True)
+    for _cam, batch_3d, batch_2d in data_loader.next_epoch():
+        if tuple(batch_3d.shape[-2:]) != (16, 3) or tuple(batch_2d.shape[-2:]) != (16, 2):
+            raise ValueError("video_mode_evaluate: 16-joint batches expected, got %s and %s"
+                             % (tuple(batch_3d.shape), tuple(batch_2d.shape)))
+        targets_3d, inputs_2d = _upload_batch(batch_3d, device), _upload_batch(batch_2d, device)
+        if args.posenet_name != 'mulit_farme_videopose':
+            inputs_2d = inputs_2d.view(-1, receptive_field, 16, 2)
+            targets_3d = targets_3d.view(-1, 1, 16, 3)
+        with torch.no_grad():
+            if flipaug:
+                outputs_3d_flip = flip_pose(model_pos_eval(flip_pose(inputs_2d)))
+                outputs_3d = model_pos_eval(inputs_2d)
+                outputs_3d = (outputs_3d + outputs_3d_flip) / 2.0
+            else:
+                outputs_3d = model_pos_eval(inputs_2d)
+        acc.add(outputs_3d, targets_3d)
+    p1, p2, pck, auc = finish(acc, get_pck_auc, key)
+    write_scalars(writer, summary, key, tag, flipaug, p1, p2, pck, auc)
+    return p1, p2, pck, auc
+
+
+def video_mode_evaluate_posenet(args, data_dict, model_pos, model_pos_eval,
+                                device, summary, writer, tag, get_pck_auc=False):
+    """Drop-in for video_mode_evaluate_posenet (:862-876): H36M without and 3DHP with the test-time flip"""
+    with torch.no_grad():
+        model_pos_eval.load_state_dict(model_pos.state_dict())
+        h36m_p1, h36m_p2, _, _ = video_mode_evaluate(args, data_dict['H36M_test'], model_pos_eval, device, summary, writer,
+                                                     key='H36M_test', tag=tag, flipaug='')
+        dhp_p1, dhp_p2, PCK, AUC = video_mode_evaluate(args, data_dict['mpi3d_loader'], model_pos_eval, device, summary,
+                                                       writer, key='mpi3d_loader', tag=tag, flipaug='_flip',
+                                                       get_pck_auc=get_pck_auc)
+    return h36m_p1, h36m_p2, dhp_p1, dhp_p2, PCK, AUC

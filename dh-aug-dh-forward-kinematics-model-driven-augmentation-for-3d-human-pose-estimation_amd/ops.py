@@ -244,6 +244,47 @@ def clip_gather(seq3d, seq2d, cams, seq_offset, seq_len, records, frames, pad, c
     return oc, o3, o2
 
 
+def eval_totals(device=None):
+    """a zeroed device totals record of pose_metrics (struct dhaug_eval_totals as int64 words: sum_err and sum_pmpjpe are
+    fp64 bit patterns, then poses and tp[32])"""
+    return torch.zeros(_lib.EVAL_TOTALS_WORDS, dtype=torch.int64, device=device if device is not None else "cuda")
+
+
+def pose_metrics(pred, target, center=False, thresholds=(), multiplicity=None, per_pose=False, totals=None):
+    """evaluation metrics of (P, 16, 3) poses (dhaug_pose_metrics): per-joint error, PCK counts and P-MPJPE.
+    thresholds: up to 32 host floats in mm (compared with fl32(error * 1000)); multiplicity: 16 host ints (joint weights of
+    the PCK counts, None = 1 each); totals: a record of eval_totals() accumulated into (stream order, no host read).
+    Returns (mpjpe, pmpjpe) as fp32 (P,) device tensors when per_pose, else (None, None)."""
+    if tuple(pred.shape) != tuple(target.shape):
+        raise ValueError("pose_metrics: pred %s and target %s differ in shape" % (tuple(pred.shape), tuple(target.shape)))
+    if pred.dim() < 2 or tuple(pred.shape[-2:]) != (16, 3):
+        raise ValueError("pose_metrics: poses must be (..., 16, 3), got %s" % (tuple(pred.shape),))
+    thr = [float(t) for t in thresholds]
+    if len(thr) > _lib.EVAL_MAX_THRESHOLDS:
+        raise ValueError("pose_metrics: at most %d thresholds, got %d" % (_lib.EVAL_MAX_THRESHOLDS, len(thr)))
+    if totals is None and not per_pose:
+        raise ValueError("pose_metrics: nothing to compute (no totals and per_pose=False)")
+    y = _dev(pred, torch.float32, "pose_metrics").reshape(-1, 48)
+    x = _dev(target, torch.float32, "pose_metrics").reshape(-1, 48)
+    P, dev = y.shape[0], y.device
+    m = None
+    if multiplicity is not None:
+        m = [int(v) for v in multiplicity]
+        if len(m) != 16 or any(v < 0 or v > _lib.EVAL_MAX_MULTIPLICITY for v in m):
+            raise ValueError("pose_metrics: multiplicity must be 16 ints in [0, %d]" % _lib.EVAL_MAX_MULTIPLICITY)
+        m = (ctypes.c_int32 * 16)(*m)
+    ws = None
+    if totals is not None:
+        assert totals.is_cuda and totals.dtype == torch.int64 and totals.numel() == _lib.EVAL_TOTALS_WORDS \
+            and totals.is_contiguous(), "pose_metrics: totals must come from eval_totals()"
+        ws = torch.empty(_lib.EVAL_WORKSPACE_BYTES // 8, dtype=torch.int64, device=dev)
+    mp = torch.empty(P, dtype=torch.float32, device=dev) if per_pose else None
+    pp = torch.empty(P, dtype=torch.float32, device=dev) if per_pose else None
+    _lib.call("dhaug_pose_metrics", _p(y), _p(x), P, int(bool(center)), (ctypes.c_double * max(1, len(thr)))(*thr),
+              len(thr), m, _p(mp), _p(pp), _p(totals), _p(ws), _stream())
+    return mp, pp
+
+
 def center_flip(x, center, flip, adjoint=False):
     C = x.shape[-1]
     v = _dev(x, torch.float32, "center_flip").reshape(-1, 16 * C)

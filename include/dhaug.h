@@ -189,6 +189,39 @@ int dhaug_clip_gather(const float* seq3d, const float* seq2d, const float* cams,
                       int frames, int pad, int causal_shift, const int8_t* perm3d, const int8_t* perm2d,
                       float* out3d, float* out2d, float* out_cam, void* stream);
 
+/* Posenet evaluation metrics of P poses, pred / target (P,16,3) fp32, both 16-byte aligned (DHAUG_EALIGN): mpjpe, p_mpjpe,
+ * compute_PCK and compute_AUC of R/utils/loss.py (:8-14, :123-164, :192-225) as evaluate (R/function_aug/model_pos_eval.py:16-92)
+ * and video_mode_evaluate (R/models_Fk_GAN/video_mode_operate.py:769-876) call them.
+ *   center != 0: both poses root-centred first, x - x[:, :1] in fp32 (what evaluate does; the loss functions do not).
+ *   joint error e_j = sqrt((dx*dx + dy*dy) + dz*dz) in fp32, d = pred - target, no contraction, correctly rounded sqrt:
+ *     numpy's value in compute_PCK bit for bit.  Joint j is a true positive at threshold k if fl32(e_j * 1000) < thresholds[k]
+ *     (compared exactly against the fp64 threshold), and then counts multiplicity[j] times.
+ *   P-MPJPE of a pose: the mean over its joints of |a * Q (pred_j - muY) + muX - target_j| after the optimal similarity
+ *     alignment (the reference's sign-fixed SVD: proper rotation, scale a = (s1 + s2 + sign * s3) * |X0| / |Y0|), in fp64.
+ *     NaN where |X0| or |Y0| is 0 (the reference's 0 / 0).
+ *   mpjpe_out, pmpjpe_out: optional fp32 (P,) per-pose MPJPE / P-MPJPE (meters, like the inputs), every element written.
+ *   totals: optional device dhaug_eval_totals, ACCUMULATED into (the caller zeroes it): sum_err += sum of all e_j (fp64),
+ *     sum_pmpjpe += sum of the per-pose P-MPJPE (fp64), poses += P, tp[k] += true positives at threshold k.  Deterministic:
+ *     per-workgroup partials in a fixed order, no atomics; the same call sequence gives bit-identical totals.
+ *   workspace: device, DHAUG_EVAL_WORKSPACE_BYTES, 8-byte aligned, needed with totals (NULL allowed without); one call at a
+ *     time per workspace (stream order).
+ *   thresholds: HOST array of nthr doubles, multiplicity: HOST array of 16 ints (NULL = all 1), both read during the call.
+ * DHAUG_EINVAL: P < 0, nthr < 0 or > DHAUG_EVAL_MAX_THRESHOLDS, thresholds NULL with nthr > 0, a multiplicity outside
+ * [0, DHAUG_EVAL_MAX_MULTIPLICITY], no output at all, totals without a workspace, or (P > 0) a NULL pred / target.
+ * DHAUG_EUNSUPPORTED: P >= 2^31.  Two launches (metrics, then the one-wave reduction when totals is given). */
+#define DHAUG_EVAL_MAX_THRESHOLDS 32
+#define DHAUG_EVAL_MAX_MULTIPLICITY 1024
+#define DHAUG_EVAL_WORKSPACE_BYTES (2048 * (3 + DHAUG_EVAL_MAX_THRESHOLDS) * 8)
+typedef struct dhaug_eval_totals {
+    double sum_err;
+    double sum_pmpjpe;
+    int64_t poses;
+    int64_t tp[DHAUG_EVAL_MAX_THRESHOLDS];
+} dhaug_eval_totals;
+int dhaug_pose_metrics(const float* pred, const float* target, int64_t P, int center, const double* thresholds, int nthr,
+                       const int32_t* multiplicity, float* mpjpe_out, float* pmpjpe_out, void* totals, void* workspace,
+                       void* stream);
+
 /* ------------------------------------------------------------------------------------------------------
  * Dense layers: bf16 MFMA GEMM with fused epilogue
  * ---------------------------------------------------------------------------------------------------- */
