@@ -29,6 +29,10 @@ SIGNATURES = {
     "dhaug_center_flip_backward": [_vp, _vp, _i64, _i32, _i32, _i32, _vp],
     "dhaug_clip_gather": [_vp, _vp, _vp, _i32, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp],
     "dhaug_pose_metrics": [_vp, _vp, _i64, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp],
+    "dhaug_pair_batch": [_vp, _vp, _i64, _i32, _i32, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "dhaug_pose_mse": [_vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp],
+    "dhaug_grad_sumsq": [_vp, _i64, _f32, _vp, _vp, _vp],
+    "dhaug_adam_clip_step": [_vp, _vp, _vp, _vp, _i64, _f32, _f32, _f32, _f32, _vp, _f32, _f32, _vp, _vp, _vp],
     "dhaug_gemm_bf16_dmask": [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _i32, _f32, _vp, _i64, _i64, _i64, _i64, _vp],
     "dhaug_gemm_bf16_dmask_pad": [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _i32, _f32, _vp, _i64, _i64, _i64, _i64, _i64, _vp],
     "dhaug_gemm_bf16_dbits": [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _i32, _f32, _vp, _i64, _i64, _vp],
@@ -144,6 +148,8 @@ EVAL_MAX_THRESHOLDS = 32
 EVAL_MAX_MULTIPLICITY = 1024
 EVAL_TOTALS_WORDS = 3 + EVAL_MAX_THRESHOLDS            # struct dhaug_eval_totals as int64 words
 EVAL_WORKSPACE_BYTES = 2048 * EVAL_TOTALS_WORDS * 8
+LOSS_METER_WORDS = 3                                   # struct dhaug_loss_meter as int64 words (word 0: fp64 bits)
+POSETRAIN_WORKSPACE_BYTES = 2048 * 8
 
 ERRORS = {-1: "DHAUG_EINVAL (bad argument)", -2: "DHAUG_EALIGN (alignment contract violated)",
           -3: "DHAUG_EUNSUPPORTED (shape not implemented)"}

@@ -5,7 +5,9 @@ video_mode_dataloader_update :898-968) kept on the device.
 The loader's sequences sit concatenated in device memory; every batch is one dhaug_clip_gather launch over a slice of the
 epoch's permuted record table (uploaded once per epoch), so there is no host work per clip and no host <-> device copy per
 batch.  Batches are device fp32 tensors; they equal the reference's float64 numpy batches cast to fp32 bit for bit (the
-gather only copies, negates and permutes)."""
+gather only copies, negates and permutes).  Also here: the posenet evaluation and training loops of the video mode
+(video_mode_evaluate, video_mode_train_posenet, GAN_dataSet_video_mode_train_posenet), see function_aug/model_pos_eval.py and
+function_aug/model_pos_train.py."""
 import numpy as np
 import torch
 
@@ -323,3 +325,69 @@ def video_mode_evaluate_posenet(args, data_dict, model_pos, model_pos_eval,
                                                        writer, key='mpi3d_loader', tag=tag, flipaug='_flip',
                                                        get_pck_auc=get_pck_auc)
     return h36m_p1, h36m_p2, dhp_p1, dhp_p2, PCK, AUC
+
+
+def _video_train_epoch(fn, title, batches, model_pos, optimizer, criterion, device, args, single_frame_targets):
+    """the epoch both video training loops share: per batch up to four steps in the reference's order -- plain, playback, flip,
+    flip + playback (R/models_Fk_GAN/video_mode_operate.py:566-629, :686-749)"""
+    from ..function_aug.model_pos_train import StepRunner, set_grad, summary_line
+    torch.set_grad_enabled(True)
+    set_grad([model_pos], True)
+    model_pos.train()
+    run = StepRunner(model_pos, optimizer, criterion, device)
+    flip, playback = bool(args.flip_pos_model_input), args.GAN_video_playback_input == True  # noqa: E712 (the reference's test)
+    for b in batches(flip, playback):
+        num_poses = b["inp"].shape[0]
+        if num_poses == 1:
+            break
+        tgt, tgt_flip = b["tgt"], b.get("tgt_flip")
+        if single_frame_targets:                                   # batch_3d.contiguous().view(-1, 1, 16, 3) (:679)
+            tgt = tgt.view(-1, 1, 16, 3)
+            tgt_flip = None if tgt_flip is None else tgt_flip.view(-1, 1, 16, 3)
+        run.step(b["inp"], tgt, "loss", num_poses)
+        if playback:
+            run.step(b["inp_back"], tgt, "back_loss", num_poses)
+        if flip:
+            # the reference updates its flip meter with the plain step's loss (:614, :734): StepRunner.finish copies the plain meter
+            run.step(b["inp_flip"], tgt_flip, None, num_poses)
+            if playback:
+                run.step(b["inp_flip_back"], tgt_flip, "back_flip_loss", num_poses)
+    fn.last_meters = run.finish(flip)
+    fn.last_trace = run.trace_tensor()
+    summary_line(title, fn.last_meters)
+
+
+def video_mode_train_posenet(model_pos, data_loader, optimizer, criterion, device, args):
+    """Drop-in for video_mode_train_posenet (R/models_Fk_GAN/video_mode_operate.py:532-648) over data_loader.next_epoch() yielding
+    (cam, batch_3d (n,F3,16,3), batch_2d (n,F2,16,2)): device tensors (this package's GAN_video_ChunkedGenerator) or host numpy
+    batches (the reference's generators).  See function_aug/model_pos_train.py for what runs where; returns None, the epoch's
+    averages are on video_mode_train_posenet.last_meters."""
+    def batches(flip, playback):
+        for _cam, batch_3d, batch_2d in data_loader.next_epoch():
+            if batch_3d.shape[0] == 1:                  # the reference's loop stops at a batch of one pose
+                return
+            yield ops.pair_batch(_upload_batch(batch_3d, device), _upload_batch(batch_2d, device), flip=flip, playback=playback)
+
+    _video_train_epoch(video_mode_train_posenet, "Train posenet (video)", batches, model_pos, optimizer, criterion, device, args,
+                       False)
+    return
+
+
+def GAN_dataSet_video_mode_train_posenet(model_pos, data_loader, optimizer, criterion,
+                                         device, args):
+    """Drop-in for GAN_dataSet_video_mode_train_posenet (:652-765) over a loader of (cam, batch_3d, batch_2d) batches, or over the
+    device-resident product of the video GAN epoch (FakePairBuffer / TensorLoader: one permutation per epoch, one launch per
+    batch).  The 3D rows are viewed as (-1, 1, 16, 3) as at :679."""
+    from ..function_aug.model_pos_train import pair_batches
+
+    def batches(flip, playback):
+        return pair_batches(data_loader, device, flip, playback, lambda batch: (batch[1], batch[2]))
+
+    _video_train_epoch(GAN_dataSet_video_mode_train_posenet, "Train posenet (GAN clips)", batches, model_pos, optimizer,
+                       criterion, device, args, True)
+    return
+
+
+for _f in (video_mode_train_posenet, GAN_dataSet_video_mode_train_posenet):
+    _f.last_meters = None
+    _f.last_trace = None

@@ -294,6 +294,124 @@ def center_flip(x, center, flip, adjoint=False):
     return out.reshape(-1, 16, C)
 
 
+# ---------------------------------------------------------------------------------------------- posenet training
+def posetrain_workspace(device=None):
+    """the partials' workspace of pose_mse / grad_sumsq / adam_clip_step (one call chain at a time per workspace)"""
+    return torch.empty(_lib.POSETRAIN_WORKSPACE_BYTES // 8, dtype=torch.int64, device=device if device is not None else "cuda")
+
+
+def loss_meters(count=1, device=None):
+    """count zeroed device meter records (struct dhaug_loss_meter as int64 words: sum_loss_x_poses as fp64 bits, poses, steps)"""
+    return torch.zeros((count, _lib.LOSS_METER_WORDS), dtype=torch.int64, device=device if device is not None else "cuda")
+
+
+def pair_batch(p3, p2, idx=None, n=None, flip=False, playback=False):
+    """the tensors of one posenet training iteration in one launch (dhaug_pair_batch).  p3 (M, [F3,] 16, 3), p2 (M, [F2,] 16, 2);
+    idx: int64 device indices into the M rows (None: rows 0..n-1, n defaulting to M).  Returns a dict: tgt (n,F3,16,3)
+    root-centred, inp (n,F2,16,2); flip: tgt_flip, inp_flip; playback: inp_back (and inp_flip_back with flip)."""
+    if p3.dim() not in (3, 4) or tuple(p3.shape[-2:]) != (16, 3):
+        raise ValueError("pair_batch: p3 must be (M, 16, 3) or (M, F, 16, 3), got %s" % (tuple(p3.shape),))
+    if p2.dim() not in (3, 4) or tuple(p2.shape[-2:]) != (16, 2):
+        raise ValueError("pair_batch: p2 must be (M, 16, 2) or (M, F, 16, 2), got %s" % (tuple(p2.shape),))
+    M = p3.shape[0]
+    if p2.shape[0] != M:
+        raise ValueError("pair_batch: p3 has %d rows, p2 %d" % (M, p2.shape[0]))
+    F3 = p3.shape[1] if p3.dim() == 4 else 1
+    F2 = p2.shape[1] if p2.dim() == 4 else 1
+    if idx is not None:
+        if idx.dim() != 1 or idx.dtype != torch.int64:
+            raise ValueError("pair_batch: idx must be a 1-D int64 tensor")
+        if n is not None and n != idx.shape[0]:
+            raise ValueError("pair_batch: n = %d but idx holds %d indices" % (n, idx.shape[0]))
+        n = idx.shape[0]
+    else:
+        n = M if n is None else int(n)
+        if n < 0 or n > M:
+            raise ValueError("pair_batch: n = %d outside 0..%d" % (n, M))
+    if F3 < 1 or F2 < 1 or n * max(F3, F2) >= (1 << 31) // 48:
+        raise ValueError("pair_batch: n * frames must be in [0, 2^31 / 48)")
+    x3 = _dev(p3, torch.float32, "pair_batch")
+    x2 = _dev(p2, torch.float32, "pair_batch")
+    ix = None if idx is None else _dev(idx, torch.int64, "pair_batch")
+    dev = x3.device
+    new = lambda F, C: torch.empty((n, F, 16, C), dtype=torch.float32, device=dev)
+    out = dict(tgt=new(F3, 3), inp=new(F2, 2))
+    if flip:
+        out.update(tgt_flip=new(F3, 3), inp_flip=new(F2, 2))
+    if playback:
+        out.update(inp_back=new(F2, 2))
+        if flip:
+            out.update(inp_flip_back=new(F2, 2))
+    g = lambda k: _p(out.get(k))
+    _lib.call("dhaug_pair_batch", _p(x3), _p(x2), M, F3, F2, _p(ix), n, int(bool(flip)), int(bool(playback)), g("tgt"), g("inp"),
+              g("tgt_flip"), g("inp_flip"), g("inp_back"), g("inp_flip_back"), _stream())
+    return out
+
+
+def pose_mse(pred, target, poses, meter=None, workspace=None, loss=None):
+    """nn.MSELoss(reduction='mean') forward + backward (dhaug_pose_mse): returns (loss, grad), loss a 1-element fp32 device
+    tensor (or the one given), grad = d loss / d pred in pred's shape.  meter: one record of loss_meters(), accumulated into
+    (AverageMeter.update(loss, poses) on the device)."""
+    if tuple(pred.shape) != tuple(target.shape):
+        raise ValueError("pose_mse: pred %s and target %s differ in shape" % (tuple(pred.shape), tuple(target.shape)))
+    if int(poses) < 0:
+        raise ValueError("pose_mse: poses must be >= 0")
+    y = _dev(pred.detach(), torch.float32, "pose_mse")
+    x = _dev(target, torch.float32, "pose_mse")
+    dev = y.device
+    if meter is not None:
+        assert meter.is_cuda and meter.dtype == torch.int64 and meter.numel() == _lib.LOSS_METER_WORDS and meter.is_contiguous(), \
+            "pose_mse: meter must be one record of loss_meters()"
+    ws = workspace if workspace is not None else posetrain_workspace(dev)
+    grad = torch.empty_like(y)
+    if loss is None:
+        loss = torch.empty(1, dtype=torch.float32, device=dev)
+    assert loss.is_cuda and loss.dtype == torch.float32 and loss.numel() == 1
+    _lib.call("dhaug_pose_mse", _p(y), _p(x), y.numel(), int(poses), _p(grad), _p(loss), _p(meter), _p(ws), _stream())
+    return loss, grad
+
+
+def _flat_f32(t, name, what):
+    if t.dim() != 1:
+        raise ValueError("%s: %s must be a flat vector, got %s" % (name, what, tuple(t.shape)))
+    if not t.is_cuda:
+        raise RuntimeError("dhaug op `%s` needs a GPU tensor (no CPU fallback exists)" % name)
+    assert t.dtype == torch.float32 and t.is_contiguous(), "%s: %s must be contiguous fp32" % (name, what)
+    return t
+
+
+def grad_sumsq(grad, grad_scale=1.0, workspace=None, step_counter=None):
+    """per-workgroup partial sums of (grad * grad_scale)^2 into workspace (dhaug_grad_sumsq); step_counter (int32 device tensor)
+    is advanced by one in the same launch.  Returns the workspace (adam_clip_step reads it)."""
+    g = _flat_f32(grad, "grad_sumsq", "grad")
+    ws = workspace if workspace is not None else posetrain_workspace(g.device)
+    assert step_counter is None or step_counter.dtype == torch.int32
+    _lib.call("dhaug_grad_sumsq", _p(g), g.numel(), float(grad_scale), _p(ws), _p(step_counter), _stream())
+    return ws
+
+
+def adam_clip_step(param, grad, exp_avg, exp_avg_sq, step_dev, workspace, max_norm, lr=1e-3, betas=(0.9, 0.999), eps=1e-8,
+                   grad_scale=1.0, norm_out=None):
+    """clip_grad_norm_(max_norm) + Adam.step() from the partials of grad_sumsq(grad, grad_scale, workspace) (dhaug_adam_clip_step);
+    *step_dev is the step count (already advanced).  Returns the gradient norm as a 1-element fp32 device tensor."""
+    n = param.numel()
+    vectors = ((param, "param"), (grad, "grad"), (exp_avg, "exp_avg"), (exp_avg_sq, "exp_avg_sq"))
+    for t, what in vectors:
+        if t.dim() != 1 or t.numel() != n:
+            raise ValueError("adam_clip_step: %s must be a flat vector of %d elements, got %s" % (what, n, tuple(t.shape)))
+    max_norm = float(max_norm)
+    if not max_norm > 0.0:
+        raise ValueError("adam_clip_step: max_norm must be > 0, got %r" % max_norm)
+    for t, what in vectors:
+        _flat_f32(t, "adam_clip_step", what)
+    assert step_dev.dtype == torch.int32
+    if norm_out is None:
+        norm_out = torch.empty(1, dtype=torch.float32, device=param.device)
+    _lib.call("dhaug_adam_clip_step", _p(param), _p(grad), _p(exp_avg), _p(exp_avg_sq), n, float(lr), betas[0], betas[1], eps,
+              _p(step_dev), float(grad_scale), max_norm, _p(workspace), _p(norm_out), _stream())
+    return norm_out
+
+
 # ---------------------------------------------------------------------------------------------- GEMM
 def cast_pad_bf16(src, pad_cols=None, out=None):
     """fp32 (rows, cols) -> bf16 (rows, pad_cols), zero-padded; out: write into these rows of a larger buffer"""

@@ -232,3 +232,62 @@ class FusedAdam(torch.optim.Optimizer):
             else:
                 work.wait()
             self._apply(ws)
+
+
+class PosenetAdam(FusedAdam):
+    """torch.optim.Adam (defaults lr 1e-3, betas (0.9, 0.999), eps 1e-8) for a posenet that stays a torch module: the flat
+    parameter / gradient / moment buffers of FusedAdam and its gradient exchange, but no bf16 weight arena (the weights are
+    Conv1d / Linear / BatchNorm tensors read by torch's own kernels), and clip_step(max_norm): clip_grad_norm_ + step as two
+    launches.  lr is read from param_groups[0]['lr'] at every step, so torch's lr schedulers and a manual decay loop work."""
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, process_group=None, data_parallel=None):
+        super().__init__(params, lr=lr, betas=betas, eps=eps, process_group=process_group, data_parallel=data_parallel)
+        self._workspace = None
+        for p in self._params:
+            del p._dhaug_grad_slot              # (the fused layers' direct accumulation assumes a bucket that zero_grad zeroes)
+            p.grad = None
+
+    def _apply(self, ws):
+        g = self.param_groups[0]
+        ops.adam_step_dev(self.flat_param, self.flat_grad, self.exp_avg, self.exp_avg_sq, self.step_dev, g["lr"],
+                          tuple(g["betas"]), g["eps"], 1.0 / ws)
+
+    def zero_grad(self, set_to_none=True):
+        """gradients are dropped, not zeroed: autograd then hands over fresh tensors (no accumulate launch per parameter), and
+        _gather_grads moves them into the flat bucket with one multi-tensor copy"""
+        self.flush()
+        for p in self._params:
+            p.grad = None
+
+    def _gather_grads(self):
+        src, dst = [], []
+        for p, gv in zip(self._params, self._views):
+            if p.grad is None:
+                gv.zero_()
+            elif p.grad.data_ptr() != gv.data_ptr():
+                src.append(p.grad)
+                dst.append(gv)
+        if dst:
+            torch._foreach_copy_(dst, src)
+
+    @torch.no_grad()
+    def clip_step(self, max_norm, norm_out=None):
+        """nn.utils.clip_grad_norm_(parameters, max_norm) followed by step(): the exchange (all-reduce sum when distributed, the
+        kernels scale by 1 / world, so the norm is that of the AVERAGED gradient), dhaug_grad_sumsq, dhaug_adam_clip_step.
+        Returns the norm as a 1-element fp32 device tensor (norm_out if given); nothing is read on the host."""
+        if not self.flat_param.is_cuda:
+            raise RuntimeError("PosenetAdam needs GPU parameters (no CPU fallback exists)")
+        max_norm = float(max_norm)
+        if not max_norm > 0.0:
+            raise ValueError("PosenetAdam.clip_step: max_norm must be > 0, got %r" % max_norm)
+        self._check_views()
+        self.flush()
+        ws = self.exchange()
+        self.step_count += 1
+        self._opt_called = True                 # what torch's lr schedulers look at to see that a step preceded scheduler.step()
+        if self._workspace is None:
+            self._workspace = ops.posetrain_workspace(self.flat_param.device)
+        g = self.param_groups[0]
+        ops.grad_sumsq(self.flat_grad, 1.0 / ws, self._workspace, self.step_dev)
+        return ops.adam_clip_step(self.flat_param, self.flat_grad, self.exp_avg, self.exp_avg_sq, self.step_dev, self._workspace,
+                                  max_norm, g["lr"], tuple(g["betas"]), g["eps"], 1.0 / ws, norm_out)

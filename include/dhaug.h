@@ -222,6 +222,57 @@ int dhaug_pose_metrics(const float* pred, const float* target, int64_t P, int ce
                        const int32_t* multiplicity, float* mpjpe_out, float* pmpjpe_out, void* totals, void* workspace,
                        void* stream);
 
+/* Posenet training: everything around the posenet call of train_posenet (R/function_aug/model_pos_train.py:13-83),
+ * video_mode_train_posenet and GAN_dataSet_video_mode_train_posenet (R/models_Fk_GAN/video_mode_operate.py:532-765).
+ *
+ * dhaug_pair_batch: the tensors one training iteration consumes, in one launch.  p3 (M,F3,16,3), p2 (M,F2,16,2) fp32 (the
+ *   reference's clips carry F2 = receptive field frames of 2D and F3 = 1 or F2 frames of 3D); idx: n int64 DEVICE row indices
+ *   into the M rows (not checked: the caller's responsibility), NULL = rows 0..n-1 (then n <= M).  Outputs, each optional, every
+ *   element of a given output written:
+ *     tgt (n,F3,16,3) = x - x[..., :1, :] per frame;  inp (n,F2,16,2) = the rows as they are;
+ *     flip != 0:      tgt_flip, inp_flip = the flip of dhaug_center_flip applied to tgt / inp;
+ *     playback != 0:  inp_back = inp with the frames reversed (torch.flip(..., dims=[1])), inp_flip_back = the same of inp_flip.
+ *   Data movement, one fp32 subtraction and a sign flip: equal to the torch expressions of the reference bit for bit.
+ *   DHAUG_EINVAL: n, M < 0, F3 or F2 < 1, no output at all, an output whose flag is off, a NULL p3 / p2 whose outputs are asked for,
+ *   n > M without idx.  All float pointers 16-byte, idx 8-byte aligned (DHAUG_EALIGN); n * max(F3, F2) < 2^31 / 48
+ *   (DHAUG_EUNSUPPORTED).  n = 0 is a no-op.
+ *
+ * dhaug_pose_mse: nn.MSELoss(reduction='mean') forward and backward of numel fp32 elements, two launches.
+ *   grad (numel) = fl32(pred - tgt) * fl32(2 / numel), every element written; *loss (device) = the mean of (pred - tgt)^2,
+ *   accumulated in fp64 from exact differences and rounded to fp32 once; meter (optional, device dhaug_loss_meter, ACCUMULATED
+ *   into): sum_loss_x_poses += (double)*loss * poses, poses += poses, steps += 1 -- AverageMeter.update(loss.item(), poses)
+ *   without the host.  workspace: device, DHAUG_POSETRAIN_WORKSPACE_BYTES, 8-byte aligned; one call at a time per workspace
+ *   (stream order).  Per-workgroup partials added in a fixed order, no atomics: the same call sequence gives the same bits.
+ *   DHAUG_EINVAL: numel or poses < 0, NULL grad / loss / workspace, (numel > 0) NULL pred / tgt.  numel = 0 is a no-op.
+ *
+ * dhaug_grad_sumsq + dhaug_adam_clip_step: nn.utils.clip_grad_norm_(params, max_norm) (error_if_nonfinite=False) followed by
+ *   torch.optim.Adam.step() on flat fp32 vectors of n elements, two launches.
+ *   dhaug_grad_sumsq writes per-workgroup fp64 partial sums of (fl32(grad[i] * grad_scale))^2 into workspace (a partition fixed by
+ *   n and grad's alignment) and, when step_counter is given, advances that device int by one (the Adam launch reads it).
+ *   dhaug_adam_clip_step (same n, grad_scale and workspace): every workgroup adds the partials in index order,
+ *   norm = fl32(sqrt(sum)), coef = min(1, max_norm / (norm + 1e-6)) in fp32 (a NaN stays a NaN), and dhaug_adam_step_dev's
+ *   arithmetic runs with the gradient (grad[i] * grad_scale) * coef; *step_dev >= 1 is the step count.  norm_out: optional device
+ *   float, what clip_grad_norm_ returns.  max_norm = +inf: no clipping.  With coef == 1 the parameters and both moments are
+ *   bit-identical to dhaug_adam_step_dev.  A NaN gradient makes every parameter NaN; an inf gradient makes coef 0, that element's
+ *   update NaN and the others' gradient 0 -- as torch.
+ *   DHAUG_EINVAL: n < 0, NULL workspace / step_dev, max_norm <= 0 or NaN, (n > 0) a NULL vector.  n = 0 is a no-op. */
+#define DHAUG_GRAD_SUMSQ_MAX_PARTIALS 1024
+#define DHAUG_POSETRAIN_WORKSPACE_BYTES (2048 * 8)
+typedef struct dhaug_loss_meter {
+    double sum_loss_x_poses;
+    int64_t poses;
+    int64_t steps;
+} dhaug_loss_meter;
+int dhaug_pair_batch(const float* p3, const float* p2, int64_t M, int F3, int F2, const int64_t* idx, int64_t n, int flip,
+                     int playback, float* tgt, float* inp, float* tgt_flip, float* inp_flip, float* inp_back,
+                     float* inp_flip_back, void* stream);
+int dhaug_pose_mse(const float* pred, const float* tgt, int64_t numel, int64_t poses, float* grad, float* loss, void* meter,
+                   void* workspace, void* stream);
+int dhaug_grad_sumsq(const float* grad, int64_t n, float grad_scale, void* workspace, int* step_counter, void* stream);
+int dhaug_adam_clip_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, float lr, float beta1,
+                         float beta2, float eps, const int* step_dev, float grad_scale, float max_norm, const void* workspace,
+                         float* norm_out, void* stream);
+
 /* ------------------------------------------------------------------------------------------------------
  * Dense layers: bf16 MFMA GEMM with fused epilogue
  * ---------------------------------------------------------------------------------------------------- */
