@@ -113,6 +113,92 @@ def test_argument_errors_are_returned_not_thrown(built):
         dhaug_amd._lib.check(-2, "x")
 
 
+def test_pose_and_elem_argument_errors(built):
+    """the pose / camera / WGAN-GP / video entry points (csrc/dhaug_pose.hip, csrc/dhaug_elem.hip): a bad argument comes back as the
+    documented code before any launch -- every pointer here is a valid HOST address, so a call that got as far as a launch would
+    return a HIP error, not -1 / -2 -- and an empty batch is a no-op that looks at no pointer"""
+    import dhaug_amd
+    L = dhaug_amd._lib.lib()
+    buf = (ctypes.c_float * 4096)()
+    base = (ctypes.addressof(buf) + 15) & ~15
+    a, b = ctypes.c_void_p(base), ctypes.c_void_p(base + 4096)
+    EINVAL, EALIGN = -1, -2
+    # frame_diff: R >= 2, w >= 1, in_w >= w, rows >= 0
+    assert L.dhaug_frame_diff(a, b, 4, 1, 48, 48, 0, None) == EINVAL
+    assert L.dhaug_frame_diff(a, b, 4, 9, 30, 48, 0, None) == EINVAL
+    assert L.dhaug_frame_diff(a, b, 4, 9, 30, 48, 1, None) == EINVAL
+    assert L.dhaug_frame_diff(a, b, 4, 9, 48, 0, 0, None) == EINVAL
+    assert L.dhaug_frame_diff(a, b, -1, 9, 48, 48, 0, None) == EINVAL
+    assert L.dhaug_frame_diff(None, b, 4, 9, 48, 48, 0, None) == EINVAL
+    assert L.dhaug_frame_diff(None, None, 0, 9, 48, 30, 1, None) == 0
+    # frame_reverse: R >= 1, w >= 1, and never in place (the rule comes after the null checks: two equal non-null addresses)
+    assert L.dhaug_frame_reverse(a, a, 4, 9, 48, None) == EINVAL
+    assert L.dhaug_frame_reverse(a, b, 4, 0, 48, None) == EINVAL
+    assert L.dhaug_frame_reverse(a, b, 4, 9, 0, None) == EINVAL
+    assert L.dhaug_frame_reverse(a, None, 4, 9, 48, None) == EINVAL
+    assert L.dhaug_frame_reverse(None, None, 0, 9, 48, None) == 0
+    # weighted_means: 1 .. 16 arrays, none null, none empty
+    n = 17
+    arrs, cnts, wts = (ctypes.c_void_p * n)(*([base] * n)), (ctypes.c_int64 * n)(*([8] * n)), (ctypes.c_float * n)(*([1.0] * n))
+    assert L.dhaug_weighted_means(arrs, cnts, wts, 0, b, None) == EINVAL
+    assert L.dhaug_weighted_means(arrs, cnts, wts, 17, b, None) == EINVAL
+    assert L.dhaug_weighted_means(arrs, cnts, wts, -1, b, None) == EINVAL
+    assert L.dhaug_weighted_means(arrs, cnts, wts, 3, None, None) == EINVAL
+    cnts[1] = 0
+    assert L.dhaug_weighted_means(arrs, cnts, wts, 3, b, None) == EINVAL
+    cnts[1], arrs[2] = 8, None
+    assert L.dhaug_weighted_means(arrs, cnts, wts, 3, b, None) == EINVAL
+    # WGAN-GP rows: W in [1, 2^20], ld_bf16 >= W, B >= 0; critic_scalars: B, P, ld >= 1
+    assert L.dhaug_gp_penalty(a, b, b, 4, (1 << 20) + 1, 0.25, None) == EINVAL
+    assert L.dhaug_gp_penalty(a, b, b, 4, 0, 0.25, None) == EINVAL
+    assert L.dhaug_gp_penalty(a, b, b, -1, 48, 0.25, None) == EINVAL
+    assert L.dhaug_gp_penalty_bf16(a, b, b, 32, b, 4, 48, 0.25, None) == EINVAL
+    assert L.dhaug_gp_penalty_bf16(a, b, b, 1 << 21, b, 4, (1 << 20) + 1, 0.25, None) == EINVAL
+    assert L.dhaug_gp_penalty(None, None, None, 0, 48, 0.25, None) == 0
+    assert L.dhaug_gp_assemble(a, a, a, b, 4, 0, None) == EINVAL
+    assert L.dhaug_gp_assemble(a, a, a, b, -1, 48, None) == EINVAL
+    assert L.dhaug_gp_assemble_bf16(a, a, a, b, b, 32, 4, 48, None) == EINVAL
+    assert L.dhaug_gp_assemble(None, None, None, None, 0, 48, None) == 0
+    assert L.dhaug_critic_scalars(a, 1, a, 0, 4, 10.0, b, b, None) == EINVAL
+    assert L.dhaug_critic_scalars(a, 1, a, 4, 0, 10.0, b, b, None) == EINVAL
+    assert L.dhaug_critic_scalars(a, 0, a, 4, 4, 10.0, b, b, None) == EINVAL
+    assert L.dhaug_critic_scalars(a, 1, a, 4, 4, 10.0, b, None, None) == EINVAL
+    # KCS: the bf16 operand's rows hold the features (ld >= W), in whole 16-byte pieces, from a 16-byte boundary
+    mis = ctypes.c_void_p(base + 4096 + 2)
+    assert L.dhaug_kcs_forward(a, None, b, 24, 4, 1, None) == EALIGN
+    assert L.dhaug_kcs_forward(a, None, b, 8, 4, 0, None) == EALIGN
+    assert L.dhaug_kcs_forward(a, None, b, 36, 4, 1, None) == EALIGN
+    assert L.dhaug_kcs_forward(a, None, mis, 32, 4, 1, None) == EALIGN
+    assert L.dhaug_kcs_forward(a, None, None, 0, 4, 1, None) == EINVAL                 # no output at all
+    assert L.dhaug_center_kcs_forward(a, b, b, 24, 4, 1, None) == EALIGN
+    assert L.dhaug_center_kcs_forward(a, None, b, 32, 4, 1, None) == EINVAL
+    assert L.dhaug_d3_penalty(a, a, a, 0.5, mis, b, b, 4, None) == EALIGN
+    # negative N, everywhere; N = 0 is a no-op
+    for N, want in ((-1, EINVAL), (0, 0)):
+        p = (lambda x: x) if N else (lambda x: None)
+        assert L.dhaug_bone_length(p(a), p(b), N, None) == want
+        assert L.dhaug_kcs_forward(p(a), p(b), None, 0, N, 1, None) == want
+        assert L.dhaug_center_kcs_forward(p(a), p(b), p(b), 32, N, 1, None) == want
+        assert L.dhaug_kcs_backward(p(a), p(a), p(b), N, 1, None) == want
+        assert L.dhaug_kcs_jvp(p(a), p(a), p(b), N, 1, None) == want
+        assert L.dhaug_d3_penalty(p(a), p(a), p(a), 0.5, p(b), p(b), p(b), N, None) == want
+        assert L.dhaug_world_to_camera_project(p(a), p(a), p(a), p(a), p(b), p(b), N, None) == want
+        assert L.dhaug_world_to_camera_project_backward(p(a), p(a), p(a), p(a), p(a), p(a), p(b), N, None) == want
+        assert L.dhaug_camera_to_world(p(a), p(a), p(a), p(b), N, None) == want
+        assert L.dhaug_bone_length_swap(p(a), p(a), p(b), N, None) == want
+        assert L.dhaug_project_to_2d(p(a), p(a), p(b), N, None) == want
+        assert L.dhaug_center_flip(p(a), p(b), N, 3, 1, 1, None) == want
+        assert L.dhaug_center_flip_backward(p(a), p(b), N, 2, 1, 1, None) == want
+    # camera: some output, and intrinsics whenever the projection is touched; centre / flip: C in {2, 3}
+    assert L.dhaug_world_to_camera_project(a, a, a, a, None, None, 4, None) == EINVAL
+    assert L.dhaug_world_to_camera_project(a, a, a, None, b, b, 4, None) == EINVAL
+    assert L.dhaug_world_to_camera_project_backward(a, a, a, None, a, a, b, 4, None) == EINVAL
+    assert L.dhaug_world_to_camera_project_backward(a, a, a, a, a, a, None, 4, None) == EINVAL
+    for C in (0, 1, 4):
+        assert L.dhaug_center_flip(a, b, 4, C, 1, 1, None) == EINVAL and L.dhaug_center_flip_backward(a, b, 4, C, 1, 1, None) == EINVAL
+        assert L.dhaug_center_flip(None, None, 0, C, 1, 1, None) == EINVAL                                    # (checked before the empty batch)
+
+
 def test_parity_program_planner_refuses_what_one_image_cannot_hold(built):
     """dhaug_mlp_forward_x3 plans the three virtual buffers of a program onto ONE in-place LDS image (+ registers + a workspace)
     on the host, before any launch: a program that reads a value from where it no longer is comes back DHAUG_EUNSUPPORTED, mixed
