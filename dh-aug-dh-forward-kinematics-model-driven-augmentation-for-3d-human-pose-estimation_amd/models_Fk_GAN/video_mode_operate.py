@@ -5,7 +5,9 @@ video_mode_dataloader_update :898-968) kept on the device.
 The loader's sequences sit concatenated in device memory; every batch is one dhaug_clip_gather launch over a slice of the
 epoch's permuted record table (uploaded once per epoch), so there is no host work per clip and no host <-> device copy per
 batch.  Batches are device fp32 tensors; they equal the reference's float64 numpy batches cast to fp32 bit for bit (the
-gather only copies, negates and permutes).  Also here: the posenet evaluation and training loops of the video mode
+gather only copies, negates and permutes).  ChunkedGenerator (:193-347) and UnchunkedGenerator (:350-406), the loaders of the
+posenet's real clips and of its evaluation sets, stand on the same plumbing with a window of their own for the 3D target
+(dhaug_clip_gather_windows, dhaug_clip_pair_batch).  Also here: the posenet evaluation and training loops of the video mode
 (video_mode_evaluate, video_mode_train_posenet, GAN_dataSet_video_mode_train_posenet), see function_aug/model_pos_eval.py and
 function_aug/model_pos_train.py."""
 import numpy as np
@@ -55,18 +57,12 @@ def _flip_perm(left, right, name):
     return perm
 
 
-class GAN_video_ChunkedGenerator:
-    """Drop-in for GAN_video_ChunkedGenerator (R/models_Fk_GAN/video_mode_operate.py:35-192).
+class _ResidentSequences:
+    """what the loaders below share: the reference's lists of per-sequence arrays checked and concatenated once on the host,
+    uploaded to the current device at the first epoch, with each sequence's first row and length beside them"""
 
-    Same signature, pair list, shuffle stream (np.random.RandomState(random_seed)), batch split and endless / state
-    resume as the reference.  Differences: next_epoch() yields (cam, poses_3d, poses_2d) as DEVICE fp32 tensors (None where
-    the reference yields None), freshly allocated per batch; next_pairs() returns the pairs as an (P, 4) int64 array also
-    without shuffle.  Poses are 16 joints: (frames, 16, 3) and (frames, 16, 2) per sequence, cameras one vector each.  The
-    lists are concatenated once here and uploaded to the current device at the first next_epoch()."""
-
-    def __init__(self, batch_size, cameras, poses_3d, poses_2d, chunk_length, pad=0, causal_shift=0, shuffle=True,
-                 random_seed=1234, augment=False, kps_left=None, kps_right=None, joints_left=None, joints_right=None,
-                 endless=False):
+    @staticmethod
+    def _check_lists(cameras, poses_3d, poses_2d):
         if poses_2d is None or len(poses_2d) == 0:
             raise ValueError("poses_2d must be a non-empty list of (frames, 16, 2) arrays")
         S = len(poses_2d)
@@ -90,25 +86,65 @@ class GAN_video_ChunkedGenerator:
             cam = [np.asarray(c).reshape(-1) for c in cameras]
             if len({c.shape[0] for c in cam}) != 1:
                 raise ValueError("cameras differ in width")
-        self._setup(batch_size, lengths, None if cam is None else cam[0].shape[0], p3 is not None, chunk_length, pad,
-                    causal_shift, shuffle, random_seed, augment, kps_left, kps_right, joints_left, joints_right, endless)
+        return lengths, cam, p3, p2
+
+    def _keep_host(self, cam, p3, p2):
         # one concatenation per construction; the upload follows at the first next_epoch()
         cat = lambda xs, w: np.concatenate([x.reshape(-1, 16, w) for x in xs]).astype(np.float32, copy=False)
         self._host = (None if cam is None else np.stack(cam).astype(np.float32, copy=False),
                       None if p3 is None else cat(p3, 3), cat(p2, 2))
         self._dev = None
 
-    @classmethod
-    def _from_device(cls, batch_size, cams, seq3d, seq2d, lengths, chunk_length, **kw):
-        """the same loader over sequences already concatenated on the device: cams (S, cam_w) or None, seq3d (T,16,3) or
-        None, seq2d (T,16,2) fp32 device tensors, lengths (S,) host integers summing to T; keyword arguments as __init__"""
-        self = cls.__new__(cls)
+    @staticmethod
+    def _check_device(cams, seq3d, seq2d, lengths):
         lengths = np.asarray(lengths, dtype=np.int64).reshape(-1)
         T = int(lengths.sum())
         if (lengths < 0).any() or tuple(seq2d.shape) != (T, 16, 2) or (seq3d is not None and tuple(seq3d.shape) != (T, 16, 3)):
             raise ValueError("device sequences do not match the lengths")
         if cams is not None and (cams.dim() != 2 or cams.shape[0] != lengths.shape[0]):
             raise ValueError("cams must be (sequences, cam_w)")
+        return lengths
+
+    def _put(self, cams, seq3d, seq2d):
+        dev = seq2d.device
+        starts = np.concatenate([[0], np.cumsum(self._lengths)[:-1]]).astype(np.int64)
+        self._dev = dict(cams=cams, seq3d=seq3d, seq2d=seq2d,
+                         offset=torch.from_numpy(starts).to(dev),
+                         length=torch.from_numpy(self._lengths.astype(np.int32)).to(dev))
+
+    def _device_data(self):
+        if self._dev is None:
+            dev = torch.device("cuda", torch.cuda.current_device())
+            up = lambda a: None if a is None else torch.from_numpy(a).to(dev)
+            cams, seq3d, seq2d = self._host
+            self._put(up(cams), up(seq3d), up(seq2d))
+            self._host = None
+        return self._dev
+
+
+class GAN_video_ChunkedGenerator(_ResidentSequences):
+    """Drop-in for GAN_video_ChunkedGenerator (R/models_Fk_GAN/video_mode_operate.py:35-192).
+
+    Same signature, pair list, shuffle stream (np.random.RandomState(random_seed)), batch split and endless / state
+    resume as the reference.  Differences: next_epoch() yields (cam, poses_3d, poses_2d) as DEVICE fp32 tensors (None where
+    the reference yields None), freshly allocated per batch; next_pairs() returns the pairs as an (P, 4) int64 array also
+    without shuffle.  Poses are 16 joints: (frames, 16, 3) and (frames, 16, 2) per sequence, cameras one vector each.  The
+    lists are concatenated once here and uploaded to the current device at the first next_epoch()."""
+
+    def __init__(self, batch_size, cameras, poses_3d, poses_2d, chunk_length, pad=0, causal_shift=0, shuffle=True,
+                 random_seed=1234, augment=False, kps_left=None, kps_right=None, joints_left=None, joints_right=None,
+                 endless=False):
+        lengths, cam, p3, p2 = self._check_lists(cameras, poses_3d, poses_2d)
+        self._setup(batch_size, lengths, None if cam is None else cam[0].shape[0], p3 is not None, chunk_length, pad,
+                    causal_shift, shuffle, random_seed, augment, kps_left, kps_right, joints_left, joints_right, endless)
+        self._keep_host(cam, p3, p2)
+
+    @classmethod
+    def _from_device(cls, batch_size, cams, seq3d, seq2d, lengths, chunk_length, **kw):
+        """the same loader over sequences already concatenated on the device: cams (S, cam_w) or None, seq3d (T,16,3) or
+        None, seq2d (T,16,2) fp32 device tensors, lengths (S,) host integers summing to T; keyword arguments as __init__"""
+        self = cls.__new__(cls)
+        lengths = cls._check_device(cams, seq3d, seq2d, lengths)
         self._setup(batch_size, lengths, None if cams is None else cams.shape[1], seq3d is not None, chunk_length, **kw)
         self._host = None
         self._put(cams, seq3d, seq2d)
@@ -158,22 +194,6 @@ class GAN_video_ChunkedGenerator:
         self.kps_left, self.kps_right, self.joints_left, self.joints_right = kps_left, kps_right, joints_left, joints_right
         self._records = (None, None)
 
-    def _put(self, cams, seq3d, seq2d):
-        dev = seq2d.device
-        starts = np.concatenate([[0], np.cumsum(self._lengths)[:-1]]).astype(np.int64)
-        self._dev = dict(cams=cams, seq3d=seq3d, seq2d=seq2d,
-                         offset=torch.from_numpy(starts).to(dev),
-                         length=torch.from_numpy(self._lengths.astype(np.int32)).to(dev))
-
-    def _device_data(self):
-        if self._dev is None:
-            dev = torch.device("cuda", torch.cuda.current_device())
-            up = lambda a: None if a is None else torch.from_numpy(a).to(dev)
-            cams, seq3d, seq2d = self._host
-            self._put(up(cams), up(seq3d), up(seq2d))
-            self._host = None
-        return self._dev
-
     @property
     def pairs(self):
         """the reference's pair list: (seq_idx, start_frame, end_frame, flip) tuples"""
@@ -206,22 +226,146 @@ class GAN_video_ChunkedGenerator:
             self._records = (pairs, torch.from_numpy(np.ascontiguousarray(pairs, dtype=np.int32)).to(dev))
         return self._records[1]
 
-    def next_epoch(self):
+    def _batches(self, launch):
+        """the epoch loop: launch(device data, this batch's slice of the record table) per batch, with the reference's endless /
+        state bookkeeping"""
         d = self._device_data()
         B = self.batch_size
         while True:
             start_idx, pairs = self.next_pairs()
             rec = self._device_records(pairs, d["seq2d"].device)
             for b in range(start_idx, self.num_batches):
-                cam, p3, p2 = ops.clip_gather(d["seq3d"], d["seq2d"], d["cams"], d["offset"], d["length"],
-                                              rec[b * B:(b + 1) * B], self.frames, self.pad, self.causal_shift,
-                                              self._perm3d, self._perm2d)
+                out = launch(d, rec[b * B:(b + 1) * B])
                 if self.endless:
                     self.state = (b + 1, pairs)
-                yield cam, p3, p2
+                yield out
             if not self.endless:
                 return
             self.state = None
+
+    def next_epoch(self):
+        return self._batches(lambda d, rec: ops.clip_gather(d["seq3d"], d["seq2d"], d["cams"], d["offset"], d["length"], rec,
+                                                            self.frames, self.pad, self.causal_shift, self._perm3d,
+                                                            self._perm2d))
+
+
+class ChunkedGenerator(GAN_video_ChunkedGenerator):
+    """Drop-in for ChunkedGenerator (R/models_Fk_GAN/video_mode_operate.py:193-347), the loader of the posenet's real clips
+    (data_dict['train_det2d3d_loader']) and, with shuffle=False, of the non-temporal posenets' validation sets (:476-511).
+
+    It differs from GAN_video_ChunkedGenerator in its 3D member: batch_3d (n, chunk_length, 16, 3) holds the frames of the
+    chunk itself, without pad and causal_shift; batch_2d (n, chunk_length + 2 pad, 16, 2) is the padded, shifted window.  Same
+    signature, pair list, RandomState(random_seed).permutation stream, batch split and endless / state resume as the reference;
+    the differences are those of GAN_video_ChunkedGenerator (device fp32 batches, one dhaug_clip_gather_windows launch each,
+    next_pairs() an int64 array), and a 2D window that lies wholly outside its sequence (a large |causal_shift|: the
+    reference's np.pad raises "can't extend empty axis" in the middle of an epoch) is a ValueError here, at construction.
+    next_epoch_pairs(flip, playback) yields what one iteration of video_mode_train_posenet reads, ops.pair_batch's dict, from
+    one dhaug_clip_pair_batch launch per batch."""
+
+    def _setup(self, batch_size, lengths, cam_w, has3d, chunk_length, pad=0, causal_shift=0, *args, **kw):
+        super()._setup(batch_size, lengths, cam_w, has3d, chunk_length, pad, causal_shift, *args, **kw)
+        self.chunk_length = self.frames - 2 * self.pad
+        seq, start, end = self._pair_arr[:, 0], self._pair_arr[:, 1], self._pair_arr[:, 2]
+        low = np.maximum(start - self.pad - self.causal_shift, 0)
+        high = np.minimum(end + self.pad - self.causal_shift, lengths[seq])
+        if (low >= high).any():
+            i = int(np.argmax(low >= high))
+            raise ValueError("pad %d, causal_shift %d: the 2D window of chunk [%d, %d) lies outside sequence %d of %d frames"
+                             % (self.pad, self.causal_shift, start[i], end[i], seq[i], lengths[seq[i]]))
+
+    def _windows(self):
+        return self.chunk_length, 0, self.frames, self.pad + self.causal_shift
+
+    def next_epoch(self):
+        return self._batches(lambda d, rec: ops.clip_gather_windows(d["seq3d"], d["seq2d"], d["cams"], d["offset"], d["length"],
+                                                                    rec, *self._windows(), self._perm3d, self._perm2d))
+
+    def next_epoch_pairs(self, flip=False, playback=False):
+        """the epoch next_epoch() yields, each batch as ops.pair_batch(batch_3d, batch_2d, flip=flip, playback=playback) would
+        make it, bit for bit, without the gathered batch in between"""
+        if not self._has3d:
+            raise ValueError("next_epoch_pairs needs poses_3d: the training targets")
+        return self._batches(lambda d, rec: ops.clip_pair_batch(d["seq3d"], d["seq2d"], d["offset"], d["length"], rec,
+                                                                *self._windows(), self._perm3d, self._perm2d, flip=flip,
+                                                                playback=playback))
+
+
+class UnchunkedGenerator(_ResidentSequences):
+    """Drop-in for UnchunkedGenerator (R/models_Fk_GAN/video_mode_operate.py:350-406), the evaluation loader of the temporal
+    posenets (data_dict['H36M_test'], data_dict['mpi3d_loader']): next_epoch() yields one sequence per batch,
+    (cam (m, cam_w), batch_3d (m, T, 16, 3), batch_2d (m, T + 2 pad, 16, 2)) with m = 2 under augment (row 1 the flipped copy),
+    else 1; None where the reference yields None.  Batches are fresh device fp32 tensors equal to the reference's float64
+    batches cast to fp32 bit for bit: the sequences are uploaded once, each batch is one dhaug_clip_gather_windows launch over the
+    records (seq, 0, T, 0[, 1]).  pad < |causal_shift| (np.pad's negative width) and an empty sequence are ValueErrors here, at
+    construction, and so are the flip lists and cameras augment cannot work with."""
+
+    def __init__(self, cameras, poses_3d, poses_2d, pad=0, causal_shift=0, augment=False, kps_left=None, kps_right=None,
+                 joints_left=None, joints_right=None):
+        lengths, cam, p3, p2 = self._check_lists(cameras, poses_3d, poses_2d)
+        self._setup(lengths, None if cam is None else cam[0].shape[0], p3 is not None, pad, causal_shift, augment, kps_left,
+                    kps_right, joints_left, joints_right)
+        self._keep_host(cam, p3, p2)
+
+    @classmethod
+    def _from_device(cls, cams, seq3d, seq2d, lengths, **kw):
+        """the same loader over sequences already concatenated on the device (see GAN_video_ChunkedGenerator._from_device)"""
+        self = cls.__new__(cls)
+        lengths = cls._check_device(cams, seq3d, seq2d, lengths)
+        self._setup(lengths, None if cams is None else cams.shape[1], seq3d is not None, **kw)
+        self._host = None
+        self._put(cams, seq3d, seq2d)
+        return self
+
+    def _setup(self, lengths, cam_w, has3d, pad=0, causal_shift=0, augment=False, kps_left=None, kps_right=None,
+               joints_left=None, joints_right=None):
+        pad = _int(pad, "pad", 0)
+        causal_shift = _int(causal_shift, "causal_shift", -(1 << 29))
+        if pad >= (1 << 29):
+            raise ValueError("pad out of range")
+        if pad < abs(causal_shift):
+            raise ValueError("pad %d < |causal_shift| %d: the 2D sequence would be padded by a negative width" % (pad, causal_shift))
+        if (lengths < 1).any():
+            raise ValueError("sequence %d is empty" % int(np.argmax(lengths < 1)))
+        if int(lengths.max()) + 2 * pad >= (1 << 31) // 12 // 2 or int(lengths.sum()) >= (1 << 31) - 1:
+            raise ValueError("sequences too long: at most 2^31 / 24 frames per padded sequence are supported")
+        self._lengths, self._cam_w, self._has3d = lengths, cam_w, has3d
+        self.pad, self.causal_shift = pad, causal_shift
+        self.kps_left, self.kps_right, self.joints_left, self.joints_right = kps_left, kps_right, joints_left, joints_right
+        self._records = None
+        self.set_augment(augment)
+
+    def num_frames(self):
+        return int(self._lengths.sum())
+
+    def augment_enabled(self):
+        return self.augment
+
+    def set_augment(self, augment):
+        self._perm2d = self._perm3d = None
+        if augment:
+            self._perm2d = _flip_perm(self.kps_left, self.kps_right, "kps")
+            if self._has3d:
+                self._perm3d = _flip_perm(self.joints_left, self.joints_right, "joints")
+            if self._cam_w is not None and self._cam_w < 8:
+                raise ValueError("augment flips camera columns 2 and 7: cameras need >= 8 columns, got %d" % self._cam_w)
+        self.augment = augment
+
+    def next_epoch(self):
+        d = self._device_data()
+        if self._records is None:
+            # rows 2s and 2s + 1: sequence s as it is and flipped; uploaded once
+            S = len(self._lengths)
+            rec = np.zeros((2 * S, 4), dtype=np.int32)
+            rec[:, 0] = np.repeat(np.arange(S), 2)
+            rec[:, 2] = np.repeat(self._lengths, 2)
+            rec[1::2, 3] = 1
+            self._records = torch.from_numpy(rec).to(d["seq2d"].device)
+        shift = self.pad + self.causal_shift
+        for s, T in enumerate(self._lengths):
+            T = int(T)
+            yield ops.clip_gather_windows(d["seq3d"], d["seq2d"], d["cams"], d["offset"], d["length"],
+                                          self._records[2 * s:2 * s + (2 if self.augment else 1)], T, 0, T + 2 * self.pad, shift,
+                                          self._perm3d, self._perm2d)
 
 
 def video_mode_random_bl_aug(x, template_idx=None):
@@ -286,7 +430,10 @@ def video_mode_evaluate(args, data_loader, model_pos_eval, device, summary=None,
                         writer=None, key='', tag='', flipaug='', get_pck_auc=False):
     """Drop-in for video_mode_evaluate (R/models_Fk_GAN/video_mode_operate.py:769-859): the reference's reshapes, posenet calls
     and flip (dhaug_center_flip per frame); the metrics are summed on the device and read once, at the end (see
-    function_aug/model_pos_eval.py).  Returns (p1 mm, p2 mm, pck %, auc %)."""
+    function_aug/model_pos_eval.py).  Returns (p1 mm, p2 mm, pck %, auc %).
+
+    data_loader.next_epoch() may yield host numpy batches (the reference's generators) or device tensors: this package's
+    UnchunkedGenerator and ChunkedGenerator(shuffle=False) are taken as they come, with no copy and no host read per batch."""
     from ..function_aug.model_pos_eval import finish, flip_pose, write_scalars
     from ..utils.loss import PoseMetricsAccumulator
 
@@ -360,9 +507,14 @@ def _video_train_epoch(fn, title, batches, model_pos, optimizer, criterion, devi
 def video_mode_train_posenet(model_pos, data_loader, optimizer, criterion, device, args):
     """Drop-in for video_mode_train_posenet (R/models_Fk_GAN/video_mode_operate.py:532-648) over data_loader.next_epoch() yielding
     (cam, batch_3d (n,F3,16,3), batch_2d (n,F2,16,2)): device tensors (this package's GAN_video_ChunkedGenerator) or host numpy
-    batches (the reference's generators).  See function_aug/model_pos_train.py for what runs where; returns None, the epoch's
+    batches (the reference's generators).  A loader with next_epoch_pairs(flip, playback) (this package's ChunkedGenerator) is asked
+    for the iteration's tensors directly: one dhaug_clip_pair_batch launch per batch from the resident sequences, the same bits.  See function_aug/model_pos_train.py for what runs where; returns None, the epoch's
     averages are on video_mode_train_posenet.last_meters."""
     def batches(flip, playback):
+        if hasattr(data_loader, "next_epoch_pairs"):    # this package's ChunkedGenerator: one launch per batch, no host batch
+            # (a batch of one pose is yielded as it is: _video_train_epoch stops there, as the reference's loop does)
+            yield from data_loader.next_epoch_pairs(flip, playback)
+            return
         for _cam, batch_3d, batch_2d in data_loader.next_epoch():
             if batch_3d.shape[0] == 1:                  # the reference's loop stops at a batch of one pose
                 return

@@ -244,6 +244,77 @@ def clip_gather(seq3d, seq2d, cams, seq_offset, seq_len, records, frames, pad, c
     return oc, o3, o2
 
 
+def _perm8(p):
+    return None if p is None else (ctypes.c_int8 * 16)(*[int(v) for v in p])
+
+
+def _clip_inputs(seq3d, seq2d, seq_offset, seq_len, records, name):
+    s2 = None if seq2d is None else _dev(seq2d, torch.float32, name).reshape(-1, 32)
+    s3 = None if seq3d is None else _dev(seq3d, torch.float32, name).reshape(-1, 48)
+    return (s3, s2, _dev(seq_offset, torch.int64, name), _dev(seq_len, torch.int32, name),
+            _dev(records, torch.int32, name).reshape(-1, 4))
+
+
+def _clip_out(t, shape, dev, name):
+    if t is None:
+        return torch.empty(shape, dtype=torch.float32, device=dev)
+    if not (t.dtype == torch.float32 and t.is_cuda and t.is_contiguous() and tuple(t.shape) == shape):
+        raise ValueError("%s: a preallocated output must be a contiguous fp32 device tensor of shape %s" % (name, shape))
+    return t
+
+
+def clip_gather_windows(seq3d, seq2d, cams, seq_offset, seq_len, records, frames3, shift3, frames2, shift2, perm3d=None,
+                        perm2d=None, out3d=None, out2d=None, out_cam=None):
+    """clip_gather with a window of its own for the 3D and the 2D frames (dhaug_clip_gather_windows): output frame f of record
+    (seq, start, end, flip) is frame clamp(start - shift + f, 0, len - 1) of the sequence.  Arguments as clip_gather; returns
+    (out_cam (nrec, cam_w), out3d (nrec, frames3, 16, 3), out2d (nrec, frames2, 16, 2)), None where the input is None."""
+    frames3, shift3, frames2, shift2 = int(frames3), int(shift3), int(frames2), int(shift2)
+    if frames3 < 1 or frames2 < 1:
+        raise ValueError("clip_gather_windows: frames3 and frames2 must be >= 1, got %d and %d" % (frames3, frames2))
+    s3, s2, off, ln, rec = _clip_inputs(seq3d, seq2d, seq_offset, seq_len, records, "clip_gather_windows")
+    c = None if cams is None else _dev(cams, torch.float32, "clip_gather_windows")
+    n, dev = rec.shape[0], s2.device
+    cam_w = 0 if c is None else c.reshape(c.shape[0], -1).shape[1]
+    o2 = _clip_out(out2d, (n, frames2, 16, 2), dev, "clip_gather_windows")
+    o3 = None if s3 is None else _clip_out(out3d, (n, frames3, 16, 3), dev, "clip_gather_windows")
+    oc = None if c is None else _clip_out(out_cam, (n, cam_w), dev, "clip_gather_windows")
+    _lib.call("dhaug_clip_gather_windows", _p(s3), _p(s2), _p(c), cam_w, _p(off), _p(ln), _p(rec), n, frames3, shift3, frames2,
+              shift2, _perm8(perm3d), _perm8(perm2d), _p(o3), _p(o2), _p(oc), _stream())
+    return oc, o3, o2
+
+
+def clip_pair_batch(seq3d, seq2d, seq_offset, seq_len, records, frames3, shift3, frames2, shift2, perm3d=None, perm2d=None,
+                    flip=False, playback=False, out=None):
+    """pair_batch of the clips clip_gather_windows would write, in one launch from the resident sequences
+    (dhaug_clip_pair_batch).  Returns pair_batch's dict: tgt (nrec, frames3, 16, 3) root-centred, inp (nrec, frames2, 16, 2);
+    flip: tgt_flip, inp_flip; playback: inp_back (and inp_flip_back with flip).  out: optional dict of preallocated outputs
+    under those names (the others are allocated)."""
+    frames3, shift3, frames2, shift2 = int(frames3), int(shift3), int(frames2), int(shift2)
+    if frames3 < 1 or frames2 < 1:
+        raise ValueError("clip_pair_batch: frames3 and frames2 must be >= 1, got %d and %d" % (frames3, frames2))
+    if seq3d is None or seq2d is None:
+        raise ValueError("clip_pair_batch: a training batch needs the 3D and the 2D sequences")
+    s3, s2, off, ln, rec = _clip_inputs(seq3d, seq2d, seq_offset, seq_len, records, "clip_pair_batch")
+    n, dev = rec.shape[0], s2.device
+    shapes = dict(tgt=(n, frames3, 16, 3), inp=(n, frames2, 16, 2))
+    if flip:
+        shapes.update(tgt_flip=shapes["tgt"], inp_flip=shapes["inp"])
+    if playback:
+        shapes.update(inp_back=shapes["inp"])
+        if flip:
+            shapes.update(inp_flip_back=shapes["inp"])
+    given = {} if out is None else out
+    if set(given) - set(shapes):
+        raise ValueError("clip_pair_batch: outputs %s are not produced with flip=%s playback=%s"
+                         % (sorted(set(given) - set(shapes)), bool(flip), bool(playback)))
+    res = {k: _clip_out(given.get(k), shape, dev, "clip_pair_batch") for k, shape in shapes.items()}
+    g = lambda k: _p(res.get(k))
+    _lib.call("dhaug_clip_pair_batch", _p(s3), _p(s2), _p(off), _p(ln), _p(rec), n, frames3, shift3, frames2, shift2,
+              _perm8(perm3d), _perm8(perm2d), int(bool(flip)), int(bool(playback)), g("tgt"), g("inp"), g("tgt_flip"),
+              g("inp_flip"), g("inp_back"), g("inp_flip_back"), _stream())
+    return res
+
+
 def eval_totals(device=None):
     """a zeroed device totals record of pose_metrics (struct dhaug_eval_totals as int64 words: sum_err and sum_pmpjpe are
     fp64 bit patterns, then poses and tp[32])"""

@@ -189,6 +189,46 @@ int dhaug_clip_gather(const float* seq3d, const float* seq2d, const float* cams,
                       int frames, int pad, int causal_shift, const int8_t* perm3d, const int8_t* perm2d,
                       float* out3d, float* out2d, float* out_cam, void* stream);
 
+/* Clip gather with a window of its own for the 3D and the 2D frames: the batches of ChunkedGenerator.next_epoch and
+ * UnchunkedGenerator.next_epoch (R/models_Fk_GAN/video_mode_operate.py:272-347, :381-406), whose 3D target is the chunk's frames
+ * and whose 2D input is the padded, shifted window.  For record i = (seq, start, end, flip):
+ *   out3d[i, f] = seq3d[seq_offset[seq] + clamp(start - shift3 + f, 0, seq_len[seq] - 1)]   f < frames3
+ *   out2d[i, f] = seq2d[seq_offset[seq] + clamp(start - shift2 + f, 0, seq_len[seq] - 1)]   f < frames2
+ * with the record's flip and the camera row as in dhaug_clip_gather.  ChunkedGenerator: (frames3, shift3) = (chunk_length, 0),
+ * (frames2, shift2) = (chunk_length + 2 pad, pad + causal_shift); UnchunkedGenerator: records (seq, 0, T, flip), (T, 0) and
+ * (T + 2 pad, pad + causal_shift).  frames3 = frames2 and shift3 = shift2 = pad + causal_shift is dhaug_clip_gather, bit for bit.
+ *   Read extents: seq3d / seq2d rows seq_offset[seq] .. seq_offset[seq] + seq_len[seq] - 1 of every record's sequence (seq_len >= 1,
+ *   seq < S: not checked, the caller builds the records); cams row seq; records rows 0 .. nrec - 1; the record's end is not read.
+ *   Outputs (nrec,frames3,16,3), (nrec,frames2,16,2), (nrec,cam_w): every element written.  Pointer pairs, permutations and
+ *   alignment as dhaug_clip_gather.
+ * DHAUG_EINVAL: nrec < 0, frames3 or frames2 < 1, seq3d / out3d or cams / out_cam not NULL together, cam_w < 1 with cameras, a
+ * perm that is not a permutation, (nrec > 0) a NULL seq2d / out2d / seq_offset / seq_len / records.  DHAUG_EUNSUPPORTED:
+ * nrec * frames3 or nrec * frames2 >= 2^31 / 12, |shift| >= 2^30.  DHAUG_EALIGN as dhaug_clip_gather.  nrec = 0 launches nothing. */
+int dhaug_clip_gather_windows(const float* seq3d, const float* seq2d, const float* cams, int cam_w,
+                              const int64_t* seq_offset, const int32_t* seq_len, const int32_t* records, int64_t nrec,
+                              int frames3, int shift3, int frames2, int shift2, const int8_t* perm3d, const int8_t* perm2d,
+                              float* out3d, float* out2d, float* out_cam, void* stream);
+
+/* dhaug_pair_batch (below) of the clips dhaug_clip_gather_windows would write, in one launch straight from the sequences: what one
+ * iteration of video_mode_train_posenet (R/models_Fk_GAN/video_mode_operate.py:532-648) reads.  With (p3, p2) = the (out3d, out2d)
+ * of dhaug_clip_gather_windows for the same records, windows and permutations, each optional output, every element written:
+ *     tgt (nrec,frames3,16,3) = p3 - p3[..., :1, :] per frame;  inp (nrec,frames2,16,2) = p2;
+ *     flip != 0:      tgt_flip, inp_flip = the H36M left/right flip of dhaug_center_flip applied to tgt / inp;
+ *     playback != 0:  inp_back = inp with the frames reversed, inp_flip_back = the same of inp_flip.
+ * Per output frame: the source index is clamped, the record's flip (perm3d / perm2d, the loader's augment) applied, then the
+ * training flip, then the frame reversal.  One fp32 subtraction, otherwise copies and signs: equal to
+ * dhaug_pair_batch(dhaug_clip_gather_windows(...)) bit for bit.
+ *   Read extents and record contract as dhaug_clip_gather_windows (no cameras).  seq3d may be NULL when neither tgt nor tgt_flip
+ *   is asked for, seq2d when no inp* is.
+ * DHAUG_EINVAL: nrec < 0, frames3 or frames2 < 1, no output at all, an output whose flag is off, a NULL seq3d / seq2d whose
+ * outputs are asked for, a perm that is not a permutation, (nrec > 0) a NULL seq_offset / seq_len / records.
+ * DHAUG_EUNSUPPORTED: nrec * frames3 or nrec * frames2 >= 2^31 / 12, |shift| >= 2^30.  DHAUG_EALIGN: a float pointer or records
+ * not 16-byte, seq_offset not 8-byte, seq_len not 4-byte aligned.  nrec = 0 launches nothing. */
+int dhaug_clip_pair_batch(const float* seq3d, const float* seq2d, const int64_t* seq_offset, const int32_t* seq_len,
+                          const int32_t* records, int64_t nrec, int frames3, int shift3, int frames2, int shift2,
+                          const int8_t* perm3d, const int8_t* perm2d, int flip, int playback, float* tgt, float* inp,
+                          float* tgt_flip, float* inp_flip, float* inp_back, float* inp_flip_back, void* stream);
+
 /* Posenet evaluation metrics of P poses, pred / target (P,16,3) fp32, both 16-byte aligned (DHAUG_EALIGN): mpjpe, p_mpjpe,
  * compute_PCK and compute_AUC of R/utils/loss.py (:8-14, :123-164, :192-225) as evaluate (R/function_aug/model_pos_eval.py:16-92)
  * and video_mode_evaluate (R/models_Fk_GAN/video_mode_operate.py:769-876) call them.
