@@ -77,7 +77,15 @@ SIGNATURES = {
     "dhaug_add_f32": [_vp, _vp, _vp, _i64, _vp],
     "dhaug_frame_reverse": [_vp, _vp, _i64, _i32, _i32, _vp],
     "dhaug_weighted_means": [ctypes.POINTER(_vp), ctypes.POINTER(_i64), ctypes.POINTER(_f32), _i32, _vp, _vp],
+    "dhaug_bn_partials": [_vp, _i32, _i64, _i64, _i64, _vp, _vp],
+    "dhaug_bn_act_forward": [_vp, _i32, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f32, _f32, _f32, _u64, _u64,
+                             _vp, _i64, _vp, _i64, _i64, _i64, _vp],
+    "dhaug_bn_act_backward_partials": [_vp, _i32, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _f32, _u64, _u64, _i64, _i64, _vp, _vp],
+    "dhaug_bn_act_backward": [_vp, _i32, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _f32, _u64, _u64, _vp, _vp, _i64, _vp, _i64, _vp,
+                              _vp, _i64, _i64, _vp],
+    "dhaug_bn_fold": [_vp, _i64, _vp, _vp, _vp, _vp, _f32, _vp, _i64, _vp, _vp, _i64, _i64, _vp],
 }
+BN_MAX_CHUNKS = 32                                     # DHAUG_BN_MAX_CHUNKS of include/dhaug.h
 
 class MlpUnit(ctypes.Structure):
     """struct dhaug_mlp_unit (include/dhaug.h)"""

@@ -94,6 +94,7 @@ def install_packed(W, nt, nn):
 def _pack(W):
     """cache entry for a weight-like fp32 (N,K) tensor.  The entry lives ON the parameter object (an id()-keyed dict
     would alias a freed parameter whose id / address get reused), and is valid for one (storage, version, epoch)."""
+    W = getattr(W, "_dhaug_owner", W)          # (a 2-D view of a Conv1d weight: the entry lives on the parameter it views)
     key = pack_key(W)
     if isinstance(W, torch.nn.Parameter):
         ent = getattr(W, "_dhaug_pack", None)
@@ -607,3 +608,48 @@ class W2CProjectFn(torch.autograd.Function):
 
 def center_flip(x, center=False, flip=False):
     return CenterFlipFn.apply(x, center, flip, False)
+
+
+# ---------------------------------------------------------------------------------------------------
+# posenet: BatchNorm1d (batch statistics) + ReLU + Dropout (+ residual) between two dense layers
+# ---------------------------------------------------------------------------------------------------
+def dropout_stream(device):
+    """(seed, offset) of the device generator for an in-kernel Philox dropout mask, as Fk_generator._jitter_stream: the offset
+    advances per call (layers get independent masks) and torch.manual_seed reproduces a run"""
+    g = torch.cuda.default_generators[device.index if device.index is not None else torch.cuda.current_device()]
+    off = g.get_offset()
+    g.set_offset(off + 4)
+    return g.initial_seed(), off
+
+
+class BnActFn(torch.autograd.Function):
+    """y = dropout_p(relu(batchnorm(z))) (+ residual), batch statistics, the module's running buffers updated in the same launch.
+    z: fp32 (M, C) or bf16 (M, ceil16 C) -- the output (and the residual) has z's type.  Saved: z, mean, rstd, gamma, beta and the
+    mask's (seed, offset); no mask tensor.  First order only."""
+
+    @staticmethod
+    def forward(ctx, z, gamma, beta, residual, bn_buffers, momentum, eps, p):
+        C = gamma.numel()
+        rng = dropout_stream(z.device) if p > 0.0 else (0, 0)
+        yb, yf, mean, rstd = ops.bn_act_forward(z, C, gamma, beta, residual=residual, buffers=bn_buffers, momentum=momentum, eps=eps,
+                                                p=p, rng=rng)
+        ctx.save_for_backward(z, mean, rstd, gamma, beta)
+        ctx.cfg = (C, p, rng, residual is not None)
+        return yb if z.dtype == BF16 else yf
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gy):
+        z, mean, rstd, gamma, beta = ctx.saved_tensors
+        C, p, rng, has_res = ctx.cfg
+        g = gy
+        if g.dtype != z.dtype:                      # (autograd hands the cotangent over in the output's type; kept for direct callers)
+            g = ops.cast_pad_bf16(g.float()[:, :C], z.shape[1]) if z.dtype == BF16 else g.float()[:, :C]
+        dzb, dzf, dgamma, dbeta = ops.bn_act_backward(z, C, g, gamma, beta, mean, rstd, p=p, rng=rng)
+        dres = gy if (has_res and ctx.needs_input_grad[3]) else None
+        return (dzb if z.dtype == BF16 else dzf), dgamma, dbeta, dres, None, None, None, None
+
+
+def bn_act(z, gamma, beta, residual=None, bn_buffers=None, momentum=0.1, eps=1e-5, p=0.0):
+    """the arithmetic follows z's type: bf16 in the 'bf16' mode, fp32 in the split modes"""
+    return BnActFn.apply(z, gamma, beta, residual, bn_buffers, momentum, eps, p)

@@ -1,0 +1,30 @@
+"""Drop-in for R/function_baseline/model_pos_preparation.py (model_pos_preparation :18-87): builds the posenet the augmentation
+trains.  Of the reference's five posenet names this package implements `videopose`, the default run's single-frame model."""
+import torch
+
+from ..models_baseline.videopose.model_VideoPose3D import TemporalModelOptimized1f
+
+POSENETS = ("videopose",)
+REFERENCE_POSENETS = ("gcn", "mlp", "videopose", "mulit_farme_videopose", "mulit_farme_poseformer")
+
+
+def model_pos_preparation(args, dataset, device, flag='train'):
+    """posenet (B,16,2) -> (B,16,3) for args.posenet_name, on `device`.  args.pretrain: load ckpt['model_pos'] from
+    args.posenet_pretrain_path (the reference globs a hard-coded empty pattern there, so the path is an attribute of its own)."""
+    name = args.posenet_name
+    if name != 'videopose':
+        known = "a posenet of the reference" if name in REFERENCE_POSENETS else "no posenet name at all"
+        raise NotImplementedError("posenet_name %r (%s) is not implemented; implemented: %s" % (name, known, ", ".join(POSENETS)))
+    widths = [1] * (int(args.stages) + 1)
+    model_pos = TemporalModelOptimized1f(16, 2, 15, filter_widths=widths, causal=False, dropout=0.25, channels=1024).to(device)
+    count = sum(p.numel() for p in model_pos.parameters())
+    print("posenet %s: %d stages, %d parameters (%.2f M), precision %s" % (name, len(widths) - 1, count, count / 1e6, model_pos.precision))
+    if getattr(args, "pretrain", False):
+        path = getattr(args, "posenet_pretrain_path", None)
+        if not path:
+            raise ValueError("args.pretrain is set: give the checkpoint as args.posenet_pretrain_path")
+        model_pos.load_state_dict(torch.load(path, map_location=device)['model_pos'])
+        print("posenet %s: weights loaded from %s" % (name, path))
+    # else: torch's default initialisation stays.  (The reference applies its init_weights here, which touches nn.Linear modules
+    # only; this model holds nn.Conv1d and nn.BatchNorm1d modules and no nn.Linear, so it is a no-op there as well.)
+    return model_pos

@@ -1142,3 +1142,108 @@ def weighted_means(arrays, weights):
     W = (ctypes.c_float * n)(*[float(w) for w in weights])
     _lib.call("dhaug_weighted_means", P, C, W, n, _p(out), _stream())
     return out.reshape(())
+
+
+# ---------------------------------------------------------------------------------------------- posenet: BatchNorm + ReLU + dropout
+def bn_workspace(C, device=None):
+    """the chunk partials between the two launches of a BatchNorm pass (DHAUG_BN_MAX_CHUNKS x 2 x C fp64; one pass at a time)"""
+    return torch.empty(_lib.BN_MAX_CHUNKS * 2 * C, dtype=torch.float64, device=device if device is not None else "cuda")
+
+
+def _bn_rows(t, C, name, what, like=None):
+    """a (M, >= C) fp32 / bf16 matrix the BatchNorm kernels read where it lies: (tensor, row pitch)"""
+    if not t.is_cuda:
+        raise RuntimeError("dhaug op `%s` needs a GPU tensor (no CPU fallback exists)" % name)
+    if t.dim() != 2 or t.shape[1] < C or t.dtype not in (torch.float32, BF16):
+        raise ValueError("%s: %s must be a fp32 or bf16 (M, >= %d) matrix, got %s %s" % (name, what, C, t.dtype, tuple(t.shape)))
+    if like is not None and (t.dtype != like.dtype or t.shape[0] != like.shape[0]):
+        raise ValueError("%s: %s must have z's dtype and rows, got %s %s" % (name, what, t.dtype, tuple(t.shape)))
+    if t.stride(1) != 1 or (t.stride(0) * t.element_size()) % 16 or t.data_ptr() % 16 or t.stride(0) < C:
+        t = t.contiguous()
+        if t.data_ptr() % 16 or (t.stride(0) * t.element_size()) % 16:
+            raise ValueError("%s: the rows of %s do not start 16-byte aligned" % (name, what))
+    return t, t.stride(0)
+
+
+def _bn_vec(t, C, name, what):
+    if not (t.is_cuda and t.dtype == torch.float32 and t.numel() == C and t.is_contiguous()):
+        raise ValueError("%s: %s must be a contiguous fp32 device vector of %d elements" % (name, what, C))
+    return t
+
+
+def _bn_outputs(M, C, dev, out_bf16, out_f32):
+    yb = torch.empty((M, ceil_to(C, 16)), dtype=BF16, device=dev) if out_bf16 else None
+    yf = torch.empty((M, C), dtype=torch.float32, device=dev) if out_f32 else None
+    return yb, yf
+
+
+def bn_act_forward(z, C, gamma, beta, residual=None, stats=None, buffers=None, momentum=0.1, eps=1e-5, p=0.0, rng=(0, 0),
+                   workspace=None, out_bf16=None, out_f32=None):
+    """y = dropout_p(relu(batchnorm(z))) (+ residual) over the first C columns of z (M, >= C; fp32 or bf16; residual of the same type),
+    dhaug_bn_partials + dhaug_bn_act_forward.  stats = (mean, rstd): the given-statistics mode (one launch, nothing updated);
+    otherwise batch statistics, and buffers = (running_mean, running_var, num_batches_tracked) are updated as nn.BatchNorm1d does.
+    rng = (seed, offset) of the dropout's Philox stream.  Returns (y_bf16 (M, ceil16 C) | None, y_f32 (M, C) | None, mean, rstd);
+    by default the output has z's type."""
+    z, ld_z = _bn_rows(z, C, "bn_act_forward", "z")
+    M, dev, zb = z.shape[0], z.device, z.dtype == BF16
+    res, ld_res = (None, 0) if residual is None else _bn_rows(residual, C, "bn_act_forward", "residual", z)
+    g, b = _bn_vec(gamma, C, "bn_act_forward", "gamma"), _bn_vec(beta, C, "bn_act_forward", "beta")
+    out_bf16 = zb if out_bf16 is None else out_bf16
+    out_f32 = (not zb) if out_f32 is None else out_f32
+    yb, yf = _bn_outputs(M, C, dev, out_bf16, out_f32)
+    rm = rv = nbt = ws = None
+    if stats is not None:
+        mean, rstd = _bn_vec(stats[0], C, "bn_act_forward", "mean"), _bn_vec(stats[1], C, "bn_act_forward", "rstd")
+    else:
+        if M == 1:
+            raise ValueError("Expected more than 1 value per channel when training, got input size %s" % (tuple(z.shape),))
+        mean, rstd = torch.empty(C, dtype=torch.float32, device=dev), torch.empty(C, dtype=torch.float32, device=dev)
+        ws = workspace if workspace is not None else bn_workspace(C, dev)
+        assert ws.is_cuda and ws.dtype == torch.float64 and ws.numel() >= _lib.BN_MAX_CHUNKS * 2 * C
+        if buffers is not None:
+            rm, rv, nbt = buffers
+            _bn_vec(rm, C, "bn_act_forward", "running_mean"), _bn_vec(rv, C, "bn_act_forward", "running_var")
+            assert nbt is None or (nbt.is_cuda and nbt.dtype == torch.int64 and nbt.numel() == 1)
+        _lib.call("dhaug_bn_partials", _p(z), int(zb), ld_z, M, C, _p(ws), _stream())
+    _lib.call("dhaug_bn_act_forward", _p(z), int(zb), ld_z, _p(res), ld_res, _p(g), _p(b), _p(mean), _p(rstd), _p(ws), _p(rm), _p(rv),
+              _p(nbt), float(momentum), float(eps), float(p), int(rng[0]), int(rng[1]), _p(yb), 0 if yb is None else yb.stride(0),
+              _p(yf), 0 if yf is None else yf.stride(0), M, C, _stream())
+    return yb, yf, mean, rstd
+
+
+def bn_act_backward(z, C, g, gamma, beta, mean, rstd, p=0.0, rng=(0, 0), workspace=None, out_bf16=None, out_f32=None):
+    """backward of bn_act_forward's branch for the cotangent g (z's type and rows): (dz_bf16 | None, dz_f32 | None, dgamma, dbeta);
+    dhaug_bn_act_backward_partials + dhaug_bn_act_backward with the forward call's (p, rng)."""
+    z, ld_z = _bn_rows(z, C, "bn_act_backward", "z")
+    g, ld_g = _bn_rows(g, C, "bn_act_backward", "g", z)
+    M, dev, zb = z.shape[0], z.device, z.dtype == BF16
+    vec = [_bn_vec(t, C, "bn_act_backward", n) for t, n in ((gamma, "gamma"), (beta, "beta"), (mean, "mean"), (rstd, "rstd"))]
+    out_bf16 = zb if out_bf16 is None else out_bf16
+    out_f32 = (not zb) if out_f32 is None else out_f32
+    dzb, dzf = _bn_outputs(M, C, dev, out_bf16, out_f32)
+    dgamma, dbeta = torch.empty(C, dtype=torch.float32, device=dev), torch.empty(C, dtype=torch.float32, device=dev)
+    ws = workspace if workspace is not None else bn_workspace(C, dev)
+    assert ws.is_cuda and ws.dtype == torch.float64 and ws.numel() >= _lib.BN_MAX_CHUNKS * 2 * C
+    head = (_p(z), int(zb), ld_z, _p(g), ld_g, _p(vec[0]), _p(vec[1]), _p(vec[2]), _p(vec[3]), float(p), int(rng[0]), int(rng[1]))
+    _lib.call("dhaug_bn_act_backward_partials", *head, M, C, _p(ws), _stream())
+    _lib.call("dhaug_bn_act_backward", *head, _p(ws), _p(dzb), 0 if dzb is None else dzb.stride(0), _p(dzf),
+              0 if dzf is None else dzf.stride(0), _p(dgamma), _p(dbeta), M, C, _stream())
+    return dzb, dzf, dgamma, dbeta
+
+
+def bn_fold(W, gamma, beta, running_mean, running_var, eps=1e-5, want_weight=True):
+    """evaluation-mode BatchNorm folded into the (N, K) layer in front of it (dhaug_bn_fold): returns (W' | None, b', rstd_run)"""
+    N = gamma.numel()
+    v = [_bn_vec(t, N, "bn_fold", n) for t, n in ((gamma, "gamma"), (beta, "beta"), (running_mean, "running_mean"),
+                                                  (running_var, "running_var"))]
+    dev = gamma.device
+    Wd = Wo = None
+    K = 0
+    if want_weight:
+        Wd = _dev(W.detach().reshape(N, -1), torch.float32, "bn_fold")
+        K = Wd.shape[1]
+        Wo = torch.empty_like(Wd)
+    bias, rstd = torch.empty(N, dtype=torch.float32, device=dev), torch.empty(N, dtype=torch.float32, device=dev)
+    _lib.call("dhaug_bn_fold", _p(Wd), K, _p(v[0]), _p(v[1]), _p(v[2]), _p(v[3]), float(eps), _p(Wo), K, _p(bias), _p(rstd), N, K,
+              _stream())
+    return Wo, bias, rstd

@@ -238,17 +238,51 @@ class PosenetAdam(FusedAdam):
     """torch.optim.Adam (defaults lr 1e-3, betas (0.9, 0.999), eps 1e-8) for a posenet that stays a torch module: the flat
     parameter / gradient / moment buffers of FusedAdam and its gradient exchange, but no bf16 weight arena (the weights are
     Conv1d / Linear / BatchNorm tensors read by torch's own kernels), and clip_step(max_norm): clip_grad_norm_ + step as two
-    launches.  lr is read from param_groups[0]['lr'] at every step, so torch's lr schedulers and a manual decay loop work."""
+    launches.  lr is read from param_groups[0]['lr'] at every step, so torch's lr schedulers and a manual decay loop work.
+    Layout: the tensors lie in the flat buffers in the order given, except that tensors whose size is no multiple of 16 bytes come
+    last (see __init__).  state_dict() records the layout; load_state_dict() refuses moments saved under another one -- for a
+    model whose tensors the rule reorders, that includes checkpoints written before the rule existed (they carry no layout)."""
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, process_group=None, data_parallel=None):
+        # tensors whose size is no multiple of 16 bytes go last in the flat buffers (a stable sort: nothing moves in a model whose only
+        # such tensor is its last bias): everything in front of them keeps 16-byte aligned storage.  The VideoPose posenet registers its
+        # 45-element output bias ahead of the convolutions, and a misaligned weight is copied before every cast to its bf16 operand.
+        given = [p for p in params]
+        params = sorted(given, key=lambda p: p.numel() % 4 != 0)
+        self._reordered = any(a is not b for a, b in zip(given, params))
         super().__init__(params, lr=lr, betas=betas, eps=eps, process_group=process_group, data_parallel=data_parallel)
         self._workspace = None
         for p in self._params:
             del p._dhaug_grad_slot              # (the fused layers' direct accumulation assumes a bucket that zero_grad zeroes)
             p.grad = None
 
+    def _layout(self):
+        return [int(p.numel()) for p in self._params]
+
+    def state_dict(self):
+        d = super().state_dict()
+        d["dhaug_flat"]["layout"] = self._layout()
+        return d
+
+    def load_state_dict(self, state_dict):
+        flat = state_dict.get("dhaug_flat")
+        if flat is not None:
+            saved = flat.get("layout")
+            if (saved is None and self._reordered) or (saved is not None and list(saved) != self._layout()):
+                raise RuntimeError("PosenetAdam.load_state_dict: the flat moments were saved under another tensor layout (%s); "
+                                   "they cannot be assigned to this optimizer's parameters"
+                                   % ("no layout recorded: a checkpoint from before tensors of odd size were placed last"
+                                      if saved is None else "sizes %s" % (list(saved)[:8],)))
+        super().load_state_dict(state_dict)
+
+    def _stale_packs(self):
+        """the kernels write the parameters through raw pointers (no version bump): any packed bf16 copy cached on one is stale"""
+        for p in self._params:
+            p._dhaug_epoch = getattr(p, "_dhaug_epoch", 0) + 1
+
     def _apply(self, ws):
         g = self.param_groups[0]
+        self._stale_packs()
         ops.adam_step_dev(self.flat_param, self.flat_grad, self.exp_avg, self.exp_avg_sq, self.step_dev, g["lr"],
                           tuple(g["betas"]), g["eps"], 1.0 / ws)
 
@@ -288,6 +322,7 @@ class PosenetAdam(FusedAdam):
         if self._workspace is None:
             self._workspace = ops.posetrain_workspace(self.flat_param.device)
         g = self.param_groups[0]
+        self._stale_packs()
         ops.grad_sumsq(self.flat_grad, 1.0 / ws, self._workspace, self.step_dev)
         return ops.adam_clip_step(self.flat_param, self.flat_grad, self.exp_avg, self.exp_avg_sq, self.step_dev, self._workspace,
                                   max_norm, g["lr"], tuple(g["betas"]), g["eps"], 1.0 / ws, norm_out)

@@ -832,6 +832,57 @@ int dhaug_rank1_bits_bf16(const uint16_t* seed, int64_t ld_seed, const uint16_t*
 /* out = a + b over n fp32 values (the branch contributions to dD/dx_hat of a multi-branch critic). */
 int dhaug_add_f32(const float* a, const float* b, float* out, int64_t n, void* stream);
 
+/* ------------------------------------------------------------------------------------------------------
+ * Single-frame VideoPose posenet: BatchNorm1d (batch statistics) + ReLU + Dropout (+ residual) between two GEMMs
+ * (R/models_baseline/videopose/model_VideoPose3D.py:163-220, TemporalModelOptimized1f._forward_blocks; every convolution there has
+ * kernel width 1 on a length-1 sequence, i.e. is a dense layer: dhaug_gemm_bf16)
+ * ----------------------------------------------------------------------------------------------------
+ * z, g, residual: (M, C) row-major with a leading dimension (elements), fp32 (z_bf16 = 0) or bf16 (z_bf16 = 1) -- all three of the
+ * one type; rows start 16-byte aligned (base 16-byte aligned, ld * element size % 16 == 0) and ld >= C (DHAUG_EALIGN otherwise).
+ * No column at or beyond C of any input row is read.  Outputs: bf16 (M, ld >= ceil16(C), ld % 8 == 0), columns [C, ceil16 C) written
+ * as zeros (directly the next GEMM's operand), and / or fp32 (M, ld >= C, ld % 4 == 0); at least one of the two.
+ * workspace: device, DHAUG_BN_MAX_CHUNKS * 2 * C doubles, 8-byte aligned: the per-chunk column sums between the two launches of a
+ * pass (stream order; one pass at a time per workspace).  fp64 accumulation in a fixed order, no atomics: the same call gives the
+ * same bits.  IEEE arithmetic; the kernels' own NaN convention: a NaN pre-activation is a NaN in y, and fails the backward pass's
+ * (pre > 0) test, so gz is 0 there.
+ *
+ * dhaug_bn_partials + dhaug_bn_act_forward (same z, M, C, workspace): mean = sum z / M, var = sum z^2 / M - mean^2 (biased),
+ *   rstd = 1 / sqrt(var + eps), each rounded to fp32 once from fp64;
+ *     y = keep * relu(fma(fl((z - mean) * rstd), gamma, beta)) * fl(1 / (1 - p)) (+ residual).
+ *   mean, rstd (C fp32 each) are written for the backward pass; running_mean / running_var (optional, both or neither) are updated as
+ *   nn.BatchNorm1d does, r = (1 - momentum) * r + momentum * (mean | var * M / (M - 1)), and *num_batches_tracked (optional, device
+ *   int64) is advanced by one.  M = 1 with batch statistics: DHAUG_EUNSUPPORTED (nn.BatchNorm1d raises).
+ *   workspace = NULL is the given-statistics mode: mean and rstd are READ, no buffer may be passed, one launch.
+ *   Dropout: keep iff word >= (uint32)(p * 2^32) with Philox4x32-10, key = seed, counter = (element index / 4, offset), element
+ *   index = row * C + column, the four words of a call deciding four consecutive elements; 0 <= p < 1 (DHAUG_EINVAL otherwise);
+ *   p = 0 draws nothing and multiplies by nothing.
+ * dhaug_bn_act_backward_partials + dhaug_bn_act_backward (same arguments): g is the cotangent of the branch output (the
+ *   residual's cotangent is g itself).  The pre-activation is recomputed by the forward kernel's own expression and the keep
+ *   decision from (seed, offset): gz = g * keep / (1 - p) where the pre-activation is > 0, exactly 0 elsewhere; xhat = (z - mean) * rstd;
+ *     dz = (gamma * rstd) * ((gz - sum gz / M) - xhat * sum(gz xhat) / M),  dgamma = sum gz xhat,  dbeta = sum gz  (optional).
+ * dhaug_bn_fold (evaluation): W_out[n, :] = gamma[n] * rstd_run[n] * W[n, :] (N, K) fp32, bias_out[n] = beta[n] - running_mean[n] *
+ *   gamma[n] * rstd_run[n], rstd_out[n] = rstd_run[n] = 1 / sqrt(running_var[n] + eps); each output optional (at least one), each
+ *   value formed in fp64 and rounded once.
+ * All: DHAUG_EINVAL for M, C, N, K < 0, a z_bf16 outside {0, 1}, p outside [0, 1), a NULL required pointer, no output; an empty
+ * batch (M = 0 or C = 0; N = 0) is a no-op that looks at no pointer. */
+#define DHAUG_BN_MAX_CHUNKS 32
+int dhaug_bn_partials(const void* z, int z_bf16, int64_t ld_z, int64_t M, int64_t C, void* workspace, void* stream);
+int dhaug_bn_act_forward(const void* z, int z_bf16, int64_t ld_z, const void* residual, int64_t ld_res, const float* gamma,
+                         const float* beta, float* mean, float* rstd, const void* workspace, float* running_mean,
+                         float* running_var, int64_t* num_batches_tracked, float momentum, float eps, float p, uint64_t seed,
+                         uint64_t offset, uint16_t* y_bf16, int64_t ld_yb, float* y_f32, int64_t ld_yf, int64_t M, int64_t C,
+                         void* stream);
+int dhaug_bn_act_backward_partials(const void* z, int z_bf16, int64_t ld_z, const void* g, int64_t ld_g, const float* gamma,
+                                   const float* beta, const float* mean, const float* rstd, float p, uint64_t seed,
+                                   uint64_t offset, int64_t M, int64_t C, void* workspace, void* stream);
+int dhaug_bn_act_backward(const void* z, int z_bf16, int64_t ld_z, const void* g, int64_t ld_g, const float* gamma,
+                          const float* beta, const float* mean, const float* rstd, float p, uint64_t seed, uint64_t offset,
+                          const void* workspace, uint16_t* dz_bf16, int64_t ld_dzb, float* dz_f32, int64_t ld_dzf, float* dgamma,
+                          float* dbeta, int64_t M, int64_t C, void* stream);
+int dhaug_bn_fold(const float* W, int64_t ldw, const float* gamma, const float* beta, const float* running_mean,
+                  const float* running_var, float eps, float* W_out, int64_t ld_out, float* bias_out, float* rstd_out, int64_t N,
+                  int64_t K, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
