@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <atomic>
 #include "dhaug.h"
 
 #define DHAUG_WAVE 64
@@ -41,6 +42,25 @@ static inline int dhaug_launch_status() {
 }
 
 static inline bool dhaug_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+
+// Lets kernel `Kern` take `bytes` of dynamic LDS (more than the 64 KB a kernel gets unasked): called in front of every launch of
+// such a kernel, it sets the attribute once per kernel instantiation AND per device -- the attribute belongs to the device's copy
+// of the kernel, so one flag per process would leave a second device's first launch with an invalid configuration.  Two threads
+// that race here both set the attribute, which is harmless; devices beyond the table set it at every launch.
+template <auto Kern>
+static inline int dhaug_dynamic_lds(int bytes) {
+    constexpr int MAX_DEVICES = 64;
+    static std::atomic<bool> done[MAX_DEVICES];                 // (static storage: all false)
+    int dev = 0;
+    hipError_t e = hipGetDevice(&dev);
+    if (e != hipSuccess) return (int)e;
+    const bool listed = dev >= 0 && dev < MAX_DEVICES;
+    if (listed && done[dev].load(std::memory_order_acquire)) return DHAUG_OK;
+    e = hipFuncSetAttribute(reinterpret_cast<const void*>(Kern), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+    if (e != hipSuccess) return (int)e;
+    if (listed) done[dev].store(true, std::memory_order_release);
+    return DHAUG_OK;
+}
 
 // Workgroups a one-per-CU (persistent) launch may take: 256, or what dhaug_set_workgroup_cap() left it -- two chains of such
 // launches on two streams then run SIDE BY SIDE on disjoint sets of CUs instead of queueing for the whole card.

@@ -18,6 +18,7 @@
 #include <cstdlib>
 #include "dhaug_common.h"
 #include "dhaug_gemm_args.h"
+#include "dhaug_gemm_route.h"
 #include <stdlib.h>
 
 namespace {
@@ -28,6 +29,7 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 using namespace dhaug_gemm;        // GemmArgs, GemmGroupArgs, apply_act, ... (dhaug_gemm_args.h)
+using namespace dhaug_route;       // the dispatchers' choice and the tile constants it shares with the kernels (dhaug_gemm_route.h)
 
 constexpr int BK = 64;
 
@@ -282,8 +284,8 @@ __global__ __launch_bounds__(256) void gemm_nt_kernel(GemmArgs p) {
 // concatenation layers, 100-wide blocks), with the global loads FOUR K-stages ahead.  gemm_nt_kernel above keeps one
 // stage in flight and drains it at every __syncthreads(): 1.8 us per 64-wide K step whatever the tile does (29.7 us for
 // a 512 x 1000 x 1000 layer, rocprof r02_video).  Here: 64 x 64 tiles (a 512-row layer still gives 128 workgroups),
-// four register stages requested up front and refilled right after their LDS write, barriers that order LDS traffic
-// only (vmcnt keeps counting across them), several workgroups per CU.
+// four stages buffered or in flight, barriers that order LDS traffic only (vmcnt keeps counting across them), several
+// workgroups per CU.
 // ---------------------------------------------------------------------------------------------------
 __device__ __forceinline__ void p_lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 __device__ __forceinline__ void p_copy16(const void* g, unsigned char* lds_wave_base) {
@@ -291,166 +293,29 @@ __device__ __forceinline__ void p_copy16(const void* g, unsigned char* lds_wave_
                                      (void __attribute__((address_space(3)))*)lds_wave_base, 16, 0, 0);
 }
 
+#ifdef DHAUG_PIPE_TIMING
+__device__ long long g_pipe_stamps[256];                       // phase stamps of gemm_block2_kernel (`tools/stamp_block2.py`)
+#endif
+
 // Operand stages travel global -> LDS without registers (global_load_lds_dwordx4, counted in vmcnt): register-staged
 // loads behind control flow make hipcc wait with small vmcnt values right behind the requests (seen in the ISA of a
 // first version), which serialises the stages again.  A stage is [64 rows][64 k] bf16 per operand, rows contiguous (the
 // copy fixes a lane's LDS slot), 16-byte chunk c of row r at position c ^ ((r >> 1) & 7) (applied on the global side).
 // Rows beyond M / N read a valid row (their results are never stored); the K tail is cut in the k-step loop.
-// *(r4, measured with `tools/time_nt_graph.py`: fifty launches replayed as one hipGraph -- the host issues a C-ABI call in ~10 us, a
-// timing loop of these launches measures the host)*  1 536 x 1000 x 1000 (the motion critics' branch layers, 435 launches per video
-// iteration): 13.3 us; without the epilogue 10.5, without fragment reads / matrix instructions 9.8, without copies 10.2, copies
-// alone 7.1 -- the phases of a stage do not overlap inside a workgroup (wait for the stage, barrier, issue the copy three stages on,
-// compute), and with 1.5 workgroups per CU little overlaps across them.  The template's other instantiation, 64 x 128 tiles with six
-// stages (one workgroup per CU, all 192 resident at once), is SLOWER (17.5 us) and is not dispatched; requesting a stage's eight
-// fragment reads before its four matrix instructions and alternating two accumulator sets (the whole-stage path below) bought 3 %.
-#ifdef DHAUG_PIPE_TIMING
-__device__ long long g_pipe_stamps[256];
-#define PIPE_STAMP(i) if (blockIdx.x == 0 && threadIdx.x == 0 && (i) < 256) g_pipe_stamps[i] = (long long)__builtin_readcyclecounter();
-#else
-#define PIPE_STAMP(i)
-#endif
-template <int BN, int NSTG>
-__global__ __launch_bounds__(256, BN == 64 ? 2 : 1) void gemm_nt_pipe_kernel(GemmArgs p) {
-    constexpr int BM = 64;
-    constexpr int TN = BN / 64;                                              // 32-column MFMA tiles per wave
-    constexpr int CS = BN + 4;
-    constexpr int STG = (BM + BN) * BK * 2;                                  // bytes per stage: 16 384 / 24 576
-    constexpr int NCP = (BM + BN) / 32;                                      // copies per lane and stage: 4 / 6
-    static_assert(NSTG * STG >= BM * CS * 4, "C tile");
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-    float* sC = reinterpret_cast<float*>(smem_raw);             // [BM][CS], reuses the staging buffers
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wm = wave >> 1, wn = wave & 1;                    // 2 x 2 waves: rows [32 wm, +32), columns [BN / 2 wn, + BN / 2)
-    const long long ntn = (p.W + BN - 1) / BN;
-    const long long m0 = (long long)(blockIdx.x / ntn) * BM;
-    const long long n0 = (long long)(blockIdx.x % ntn) * BN;
-    const int nkt = (int)((p.K + BK - 1) / BK);
-
-    // copy i of wave w moves rows [8 (4 i + w), +8) of the stage image (A rows first, then B rows): 8 lanes per row
-    const uint16_t* pg[NCP];
-    int rowoff[NCP];
-#pragma unroll
-    for (int i = 0; i < NCP; ++i) {
-        const int row0 = (4 * i + wave) * 8, row = row0 + (lane >> 3), c = (lane & 7) ^ ((row >> 1) & 7);
-        if (i < BM / 32) {
-            const long long gm = m0 + row;
-            pg[i] = p.A + (gm < p.M ? gm : p.M - 1) * p.lda + c * 8;
-        } else {
-            const long long gn = n0 + row - BM;
-            pg[i] = p.B + (gn < p.N ? gn : p.N - 1) * p.ldb + c * 8;
-        }
-        rowoff[i] = row0 * (BK * 2);
-    }
-    auto copy_stage = [&](int kt) {
-        unsigned char* base = smem_raw + (kt % NSTG) * STG;
-        long long k0 = (long long)kt * BK;
-        if (k0 + BK > p.K) k0 = p.K - BK > 0 ? p.K - BK : 0;   // short last stage: re-read the last full window (K >= 64) ...
-#pragma unroll                                                 // ... and skip its first columns in the k-step loop
-        for (int i = 0; i < NCP; ++i) p_copy16(pg[i] + k0, base + rowoff[i]);
-    };
-    f32x16 acc[TN], acc2[TN];
-#pragma unroll
-    for (int u = 0; u < TN; ++u)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) { acc[u][r] = 0.0f; acc2[u][r] = 0.0f; }
-#pragma unroll
-    for (int s = 0; s < NSTG - 1; ++s)
-        if (s < nkt && !(p.abl & 4)) copy_stage(s);
-    const int rowa = wm * 32 + (lane & 31);
-    PIPE_STAMP(0)
-    for (int kt = 0; kt < nkt; ++kt) {
-        // stage kt must have landed; younger: stages kt+1 .. kt+NSTG-2 (NCP copies each) where they exist
-        const int younger = nkt - 1 - kt;
-        PIPE_STAMP(4 + 4 * kt)
-        if (NSTG >= 6 && younger >= 4) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(4 * NCP) : "memory");
-        else if (NSTG >= 5 && younger == 3) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(3 * NCP) : "memory");
-        else if (younger >= 2) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * NCP) : "memory");
-        else if (younger == 1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NCP) : "memory");
-        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        PIPE_STAMP(5 + 4 * kt)
-        p_lds_barrier();                                        // everybody's copies of stage kt are in LDS, stage kt-1 is released
-        PIPE_STAMP(6 + 4 * kt)
-        if (kt + NSTG - 1 < nkt && !(p.abl & 4)) copy_stage(kt + NSTG - 1);
-        PIPE_STAMP(7 + 4 * kt)
-        if (p.abl & 2) continue;
-        const unsigned char* bufA = smem_raw + (kt % NSTG) * STG;
-        const unsigned char* bufB = bufA + BM * BK * 2;
-        // k-steps of this stage: a short last stage was loaded as the last full 64-wide window, its first columns belong
-        // to the previous stage
-        const long long kbeg = (long long)kt * BK;
-        int ks0 = 0;
-        if (kbeg + BK > p.K && p.K >= BK) ks0 = (int)((kbeg - (p.K - BK)) >> 4);
-        const int ks1 = p.K >= BK ? 4 : (int)(p.K >> 4);
-        if (ks0 == 0 && ks1 == 4) {
-            // a whole stage (all but a K tail): every fragment read is requested before the first matrix instruction, and the
-            // k-steps alternate between two accumulator sets.  The loop below, with its run-time bounds, is compiled as read ->
-            // wait -> MFMA per k-step on one accumulator: four LDS latencies plus four dependent matrix instructions per stage
-            // -- *(measured, hipGraph replay, 512 x 1000 x 1000: one workgroup per CU)* 9.2 us of a 10.1 us launch with the copies
-            // switched off.
-            bf16x8 fx[4], fw[4][TN];
-#pragma unroll
-            for (int ks = 0; ks < 4; ++ks) {
-                const int chunk = 2 * ks + (lane >> 5);
-                fx[ks] = *reinterpret_cast<const bf16x8*>(bufA + rowa * (BK * 2) + ((chunk ^ ((rowa >> 1) & 7)) << 4));
-#pragma unroll
-                for (int u = 0; u < TN; ++u) {
-                    const int rowb = wn * (BN / 2) + 32 * u + (lane & 31);
-                    fw[ks][u] = *reinterpret_cast<const bf16x8*>(bufB + rowb * (BK * 2) + ((chunk ^ ((rowb >> 1) & 7)) << 4));
-                }
-            }
-            __builtin_amdgcn_sched_barrier(0);                  // (left alone the scheduler sinks every read next to its MFMA,
-                                                                //  with a full lgkmcnt(0) in front of each)
-#pragma unroll
-            for (int ks = 0; ks < 4; ++ks)
-#pragma unroll
-                for (int u = 0; u < TN; ++u) {
-                    if (ks & 1) acc2[u] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fw[ks][u], fx[ks], acc2[u], 0, 0, 0);
-                    else acc[u] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fw[ks][u], fx[ks], acc[u], 0, 0, 0);
-                }
-            continue;
-        }
-        for (int ks = ks0; ks < ks1; ++ks) {
-            const int chunk = 2 * ks + (lane >> 5);
-            const bf16x8 fx = *reinterpret_cast<const bf16x8*>(bufA + rowa * (BK * 2) + ((chunk ^ ((rowa >> 1) & 7)) << 4));
-#pragma unroll
-            for (int u = 0; u < TN; ++u) {
-                const int rowb = wn * (BN / 2) + 32 * u + (lane & 31);
-                const bf16x8 fw = *reinterpret_cast<const bf16x8*>(bufB + rowb * (BK * 2) + ((chunk ^ ((rowb >> 1) & 7)) << 4));
-                acc[u] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fw, fx, acc[u], 0, 0, 0);
-            }
-        }
-    }
-#pragma unroll
-    for (int u = 0; u < TN; ++u)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[u][r] += acc2[u][r];
-    PIPE_STAMP(1)
-    if (p.abl & 1) return;
-    p_lds_barrier();                                            // the staging buffers become the C tile
-    {
-        const int m = wm * 32 + (lane & 31);
-#pragma unroll
-        for (int u = 0; u < TN; ++u)
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                const int n = wn * (BN / 2) + 32 * u + 8 * g + 4 * (lane >> 5);
-                f32x4 v = {acc[u][4 * g], acc[u][4 * g + 1], acc[u][4 * g + 2], acc[u][4 * g + 3]};
-                *reinterpret_cast<f32x4*>(sC + m * CS + n) = v;
-            }
-    }
-    p_lds_barrier();
-    PIPE_STAMP(2)
-    nt_store_tile<BM, BN>(p, sC, m0, n0, tid);
-    PIPE_STAMP(3)
-}
-
-// *(r4)* The same 64 x 64 tiles with the fragment reads taken out of the stage's critical path.  Phase stamps of the kernel above
-// (`tools/stamp_pipe.py`, one workgroup per CU): a stage is wait + barrier, ~300 clocks of copy issue, and ~600 of "read eight
-// fragments, wait for them, four matrix instructions" -- nothing of it overlaps.  Here the fragments of stage kt + 1 are requested
-// right behind the barrier that publishes them and travel under the matrix instructions of stage kt (two fragment sets, the k loop
-// unrolled by two); a stage's buffer is free as soon as its fragments are in registers, so the copy issued behind the barrier is
-// stage kt + 4's: FOUR stages buffered or in flight with the same four buffers.
+// *(r4)* The predecessor of this kernel (retired: the same tiles and copies, three stages ahead, a stage's fragments read inside
+// the stage) *(measured with `tools/time_nt_graph.py`: fifty launches replayed as one hipGraph -- the host issues a C-ABI call in
+// ~10 us, a timing loop of these launches measures the host)* took 13.3 us at 1 536 x 1000 x 1000 (the motion critics' branch layers,
+// 435 launches per video iteration): without the epilogue 10.5, without fragment reads / matrix instructions 9.8, without copies
+// 10.2, copies alone 7.1 -- the phases of a stage did not overlap inside a workgroup (wait for the stage, barrier, issue the copy
+// three stages on, compute), and with 1.5 workgroups per CU little overlaps across them.  64 x 128 tiles with six stages (one
+// workgroup per CU, all 192 resident at once) were SLOWER (17.5 us); requesting a stage's eight fragment reads before its four
+// matrix instructions bought 3 % (reads inside a loop with run-time bounds compile as read -> wait -> MFMA per k-step: 9.2 us of a
+// 10.1 us launch at 512 x 1000 x 1000 with the copies switched off).  Its phase stamps (one workgroup per CU): a stage was wait +
+// barrier, ~300 clocks of copy issue, and ~600 of "read eight fragments, wait for them, four matrix instructions" -- nothing of it
+// overlapped.  Here the fragments of stage kt + 1 are requested right behind the barrier that publishes them and travel under the
+// matrix instructions of stage kt (two fragment sets, the k loop unrolled by two); a stage's buffer is free as soon as its
+// fragments are in registers, so the copy issued behind the barrier is stage kt + 4's: FOUR stages buffered or in flight with the
+// same four buffers.
 __device__ __forceinline__ void nt_pipe2_body(const GemmArgs& p, long long tile) {
     constexpr int BM = 64, BN = 64, NSTG = 4, NCP = 4;
     constexpr int CS = BN + 4;
@@ -882,7 +747,7 @@ __global__ __launch_bounds__(256, 1) void gemm_nt_big_kernel(GemmArgs p) {
 // 256 accumulator registers + two fragment sets leave hipcc 96 spilled registers inside the k loop, and scratch reloads are entries of
 // the memory counter the stage waits count.
 // ---------------------------------------------------------------------------------------------------
-constexpr int W_BM = 256, W_BN = 256, W_BK = 32, W_NSTG = 5;
+constexpr int W_BK = 32, W_NSTG = 5;                             // (W_BM = W_BN = 256: dhaug_gemm_route.h)
 constexpr int W_STG = (W_BM + W_BN) * W_BK * 2;                              // 32 768 bytes per stage
 constexpr int W_LDS = W_NSTG * W_STG;                                        // 163 840: all of the CU's LDS
 constexpr int W_CS = W_BN + 4;
@@ -1013,8 +878,8 @@ struct TnArgs {
     long long cs_rows;             // the column sums cover rows [0, cs_rows) only (a multiple of the stage height)
 };
 
-constexpr int TN_BN = 64;           // output tile edge: small tiles keep the split-K partial sums (fp32 atomics, the
-                                    // scarce resource: ~1.3 TB/s chip-wide) at splits x N1 x N2 x 4 B with few splits
+// TN_BN = 64 (dhaug_gemm_route.h), the output tile edge: small tiles keep the split-K partial sums (fp32 atomics, the
+// scarce resource: ~1.3 TB/s chip-wide) at splits x N1 x N2 x 4 B with few splits
 constexpr int TN_LD = 96;           // LDS row stride (elements): 192 B = 48 banks, so the 4 rows of a transpose-read
                                     // block (64 B each) land on disjoint bank quarters
 
@@ -1119,18 +984,11 @@ __global__ __launch_bounds__(256) void gemm_tn_kernel(TnArgs p) {
 // stored at position c ^ (4 * ((r >> 1) & 1)): the four rows x four column groups of a transpose-read then cover all
 // 64 banks once (the copy applies the permutation on the global side).
 // ---------------------------------------------------------------------------------------------------
-__device__ __forceinline__ void f_lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-
 __device__ __forceinline__ uint32_t f_pack_bf16x2(float a, float b) {
     typedef __bf16 bf2 __attribute__((ext_vector_type(2)));
     typedef float f2 __attribute__((ext_vector_type(2)));
     const f2 v = {a, b};
     return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, bf2));
-}
-
-__device__ __forceinline__ void f_copy16(const void* g, unsigned char* lds_wave_base) {
-    __builtin_amdgcn_global_load_lds((const void __attribute__((address_space(1)))*)g,
-                                     (void __attribute__((address_space(3)))*)lds_wave_base, 16, 0, 0);
 }
 
 // The same copy for the TN kernels below, as inline assembly ON PURPOSE: their fragments are read with the hardware
@@ -1143,22 +1001,19 @@ __device__ __forceinline__ void tn_copy16(const void* g, unsigned char* lds_wave
     asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off" ::"s"((tn_lds_ptr)lds_wave_base), "v"(g) : "memory");
 }
 
-constexpr int TF_ROWS = 128;                                    // contraction rows per stage
+// (TF_ROWS = 128 contraction rows per stage: dhaug_gemm_route.h)
 
-// fragment of 8 contraction rows x 16 columns from a stage whose rows hold CH 16-byte chunks (CH = 8: 64 columns,
-// chunk c of row r at position c ^ (4 * ((r >> 1) & 1)); CH = 16: 128 columns, position c ^ (4 * (r & 3))): in both
-// layouts the four rows x four column groups of a transpose-read cover all 64 banks once
-template <int CH>
-__device__ __forceinline__ int tf_sw(int row) { return CH == 8 ? ((row >> 1) & 1) << 2 : (row & 3) << 2; }
+// fragment of 8 contraction rows x 16 columns from a stage whose rows hold eight 16-byte chunks (64 columns), chunk c of row r
+// at position c ^ (4 * ((r >> 1) & 1)): the four rows x four column groups of a transpose-read cover all 64 banks once
+__device__ __forceinline__ int tf_sw(int row) { return ((row >> 1) & 1) << 2; }
 
-template <int CH>
 __device__ __forceinline__ bf16x8 tf_frag(const unsigned char* stage, int kbase, int col0, int lane) {
     const int li = lane & 15, q = li >> 2, pp = li & 3;
     const int c = (col0 >> 3) + (pp >> 1), in = (pp & 1) << 3;
     const int r0 = kbase + q, r1 = r0 + 4;
     typedef bf16x4 __attribute__((address_space(3))) * lds_ptr;
-    bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_ptr)(stage + r0 * (CH * 16) + ((c ^ tf_sw<CH>(r0)) << 4) + in));
-    bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_ptr)(stage + r1 * (CH * 16) + ((c ^ tf_sw<CH>(r1)) << 4) + in));
+    bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_ptr)(stage + r0 * 128 + ((c ^ tf_sw(r0)) << 4) + in));
+    bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_ptr)(stage + r1 * 128 + ((c ^ tf_sw(r1)) << 4) + in));
     bf16x8 f = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
     return f;
 }
@@ -1168,16 +1023,18 @@ __device__ __forceinline__ bf16x8 tf_frag(const unsigned char* stage, int kbase,
 // every wave, and the tile's unused rows / columns contribute nothing
 __device__ uint4 g_tn_zero16 = {0u, 0u, 0u, 0u};
 
-// TM x 64 output tile (TM = 64 or 128 rows of C = columns of A), one batch slice.
-template <int TM>
-__global__ __launch_bounds__(256, TM == 64 ? 2 : 1) void gemm_tn64_kernel(TnArgs p) {
-    constexpr int CHA = TM / 8, RT = TM / 64;                   // chunks per A row, MFMA row tiles per wave
-    constexpr int SA = TF_ROWS * TM * 2, SB = TF_ROWS * 128;    // stage bytes
-    constexpr int NCOPY = (TF_ROWS * CHA + TF_ROWS * 8) / 256;  // copies per lane and stage
+// 64 x 64 output tile (64 rows of C = columns of A), one batch slice.  (128 x 64 tiles, one workgroup per CU, re-read less from L2
+// but measured slower -- 35 vs 27 us at 65536 x 256 x 256: the loop is bound by requests in flight, not by L2 bandwidth.  128 x 128
+// tiles, 64-row stages, four in the ring, a wave per 64 x 64 quadrant, halve the L2 -> LDS traffic again -- at 3B = 196 608 rows and
+// N1 = N2 = 256 the 64 x 64 tiles move 805 MB per layer, 62 us per launch = 21 B/clk/CU of LDS-DMA, against 33 us of HBM and 10 us
+// of matrix pipe -- and were slower too: 12.5 against 11.1 ms per GAN iteration, one wave per SIMD hides less than two workgroups
+// per CU do, and the atomic traffic doubles.  Both are retired.)
+__global__ __launch_bounds__(256, 2) void gemm_tn64_kernel(TnArgs p) {
+    constexpr int SA = TF_ROWS * 128, SB = TF_ROWS * 128;       // stage bytes
     extern __shared__ __attribute__((aligned(16))) unsigned char tsm[];       // [2 stages][A | B]
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int w1 = wave >> 1, w2 = wave & 1;                    // 2 x 2 waves: rows [RT*32*w1, ...), columns [32*w2, +32)
+    const int w1 = wave >> 1, w2 = wave & 1;                    // 2 x 2 waves: rows [32*w1, +32), columns [32*w2, +32)
     const long long nt2 = (p.N2 + TN_BN - 1) / TN_BN;
     long long tile, split;
     if ((p.nsplits & 7) == 0) {
@@ -1188,7 +1045,7 @@ __global__ __launch_bounds__(256, TM == 64 ? 2 : 1) void gemm_tn64_kernel(TnArgs
         tile = blockIdx.x % p.ntiles;
         split = blockIdx.x / p.ntiles;
     }
-    const long long n1_0 = (tile / nt2) * TM, n2_0 = (tile % nt2) * TN_BN;
+    const long long n1_0 = (tile / nt2) * TN_BN, n2_0 = (tile % nt2) * TN_BN;
     const long long ms = split * p.rows_per_split;
     long long me = ms + p.rows_per_split;
     if (me > p.M) me = p.M;
@@ -1196,30 +1053,27 @@ __global__ __launch_bounds__(256, TM == 64 ? 2 : 1) void gemm_tn64_kernel(TnArgs
     const int nst = (int)((me - ms) / TF_ROWS);                 // whole stages (checked on the host)
     const long long n1c = (p.N1 + 7) & ~7LL, n2c = (p.N2 + 7) & ~7LL;    // readable columns (the operands' rows are padded to 8)
 
-    auto copy_stage = [&](int st, int buf) {                    // asynchronous: NCOPY copies per lane, counted in vmcnt
+    auto copy_stage = [&](int st, int buf) {                    // asynchronous: 8 copies per lane, counted in vmcnt
         const long long m0 = ms + (long long)st * TF_ROWS;
         unsigned char* base = tsm + buf * (SA + SB);
 #pragma unroll
-        for (int i = 0; i < TF_ROWS * CHA / 256; ++i) {
-            constexpr int RW = 64 / CHA;                        // rows per wave instruction
-            const int row0 = (wave * (TF_ROWS * CHA / 256) + i) * RW, row = row0 + lane / CHA, c = (lane % CHA) ^ tf_sw<CHA>(row);
+        for (int i = 0; i < 4; ++i) {                           // 8 chunks per row: 8 rows per wave instruction
+            const int row0 = (wave * 4 + i) * 8, row = row0 + (lane >> 3), c = (lane & 7) ^ tf_sw(row);
             const bool in = n1_0 + c * 8 < n1c;
             tn_copy16(in ? static_cast<const void*>(p.A + (m0 + row) * p.lda + n1_0 + c * 8) : static_cast<const void*>(&g_tn_zero16),
-                     base + row0 * (CHA * 16));
+                     base + row0 * 128);
         }
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-            const int row0 = (wave * 4 + i) * 8, row = row0 + (lane >> 3), c = (lane & 7) ^ tf_sw<8>(row);
+            const int row0 = (wave * 4 + i) * 8, row = row0 + (lane >> 3), c = (lane & 7) ^ tf_sw(row);
             const bool in = n2_0 + c * 8 < n2c;
             tn_copy16(in ? static_cast<const void*>(p.B + (m0 + row) * p.ldb + n2_0 + c * 8) : static_cast<const void*>(&g_tn_zero16),
                      base + SA + row0 * 128);
         }
     };
-    f32x16 acc[RT], accs[RT];
+    f32x16 acc, accs;
 #pragma unroll
-    for (int t = 0; t < RT; ++t)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) { acc[t][r] = 0.0f; accs[t][r] = 0.0f; }
+    for (int r = 0; r < 16; ++r) { acc[r] = 0.0f; accs[r] = 0.0f; }
     const bool do_cs = p.colsum != nullptr && (tile % nt2) == 0 && w2 == 0;
     const bf16x8 ones = {0x3F80, 0x3F80, 0x3F80, 0x3F80, 0x3F80, 0x3F80, 0x3F80, 0x3F80};
     const int grp = lane >> 4;                                  // 16-lane group: columns 16*(grp&1), k half grp>>1
@@ -1228,145 +1082,30 @@ __global__ __launch_bounds__(256, TM == 64 ? 2 : 1) void gemm_tn64_kernel(TnArgs
     if (nst > 1) copy_stage(1, 1);
     for (int st = 0; st < nst; ++st) {
         const int buf = st & 1;
-        if (st + 1 < nst) {                                     // this stage landed, the next may still fly
-            if (NCOPY == 8) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-            else asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
-        } else {
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        }
-        f_lds_barrier();
+        if (st + 1 < nst) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");   // this stage landed, the next (8 copies) may still fly
+        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        p_lds_barrier();
         const unsigned char* sa = tsm + buf * (SA + SB);
         const unsigned char* sb = sa + SA;
         const bool cs_stage = do_cs && ms + (long long)st * TF_ROWS < p.cs_rows;       // wave-uniform
 #pragma unroll
         for (int ks = 0; ks < TF_ROWS / 16; ++ks) {
             const int kbase = 16 * ks + 8 * (grp >> 1);
-            const bf16x8 fb = tf_frag<8>(sb, kbase, w2 * 32 + 16 * (grp & 1), lane);
-#pragma unroll
-            for (int t = 0; t < RT; ++t) {
-                const bf16x8 fa = tf_frag<CHA>(sa, kbase, (w1 * RT + t) * 32 + 16 * (grp & 1), lane);
-                acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa, fb, acc[t], 0, 0, 0);
-                if (cs_stage) accs[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa, ones, accs[t], 0, 0, 0);
-            }
+            const bf16x8 fb = tf_frag(sb, kbase, w2 * 32 + 16 * (grp & 1), lane);
+            const bf16x8 fa = tf_frag(sa, kbase, w1 * 32 + 16 * (grp & 1), lane);
+            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa, fb, acc, 0, 0, 0);
+            if (cs_stage) accs = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa, ones, accs, 0, 0, 0);
         }
-        f_lds_barrier();                                        // every wave is done with this stage
+        p_lds_barrier();                                        // every wave is done with this stage
         if (st + 2 < nst) copy_stage(st + 2, buf);
     }
     const long long n2 = n2_0 + w2 * 32 + (lane & 31);
 #pragma unroll
-    for (int t = 0; t < RT; ++t)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const long long n1 = n1_0 + (w1 * RT + t) * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-            if (n1 < p.N1 && n2 < p.N2) atomicAdd(p.C + n1 * p.ldc + n2, acc[t][r]);
-            if (do_cs && (lane & 31) == 0 && n1 < p.N1) atomicAdd(p.colsum + n1, accs[t][r]);
-        }
-}
-
-// ---------------------------------------------------------------------------------------------------
-// 128 x 128 output tiles for the long contractions of the explicit critic step (3B rows, N1 = N2 = 256).  With 64 x 64
-// tiles every row of both operands crosses L2 -> LDS four times (16 tiles x 128 B of 512 B each): 805 MB per layer at
-// 3B = 196 608 rows, and the measured 62 us per launch is 21 B/clk/CU of LDS-DMA -- the kernel is bound by the L2 -> CU
-// path, not by HBM (33 us) or the matrix pipe (10 us).  128 x 128 tiles halve that traffic.  64-row stages of 32 KB
-// (both operands), four in the ring (three in flight), one workgroup per CU; a wave owns a 64 x 64 quadrant.
-// RESULT (measured): correct (tests/test_gpu_kernels.py::test_gemm_tn) but slower -- the GAN iteration takes 12.5 ms with
-// it against 11.1 ms with the 64 x 64 tiles, with and without fragment reads one k-step ahead: one wave per SIMD hides
-// less than two workgroups per CU do, and the atomic traffic doubles (64 slices x 256 KB).  Not used by default
-// (DHAUG_TN_128=1 selects it).
-// ---------------------------------------------------------------------------------------------------
-constexpr int TB_ROWS = 64, TB_STG = 2 * TB_ROWS * 256, TB_NSTG = 4;           // 32 768 bytes per stage
-
-__global__ __launch_bounds__(256, 1) void gemm_tn128_kernel(TnArgs p) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char tsm[];       // [4 stages][A 16 KB | B 16 KB]
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int w1 = wave >> 1, w2 = wave & 1;                    // quadrant: C rows [64 w1, +64), columns [64 w2, +64)
-    const long long nt2 = p.N2 / 128;
-    long long tile, split;
-    if ((p.nsplits & 7) == 0) {
-        const long long xcd = blockIdx.x & 7, local = blockIdx.x >> 3;
-        tile = local % p.ntiles;
-        split = xcd + 8 * (local / p.ntiles);
-    } else {
-        tile = blockIdx.x % p.ntiles;
-        split = blockIdx.x / p.ntiles;
+    for (int r = 0; r < 16; ++r) {
+        const long long n1 = n1_0 + w1 * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+        if (n1 < p.N1 && n2 < p.N2) atomicAdd(p.C + n1 * p.ldc + n2, acc[r]);
+        if (do_cs && (lane & 31) == 0 && n1 < p.N1) atomicAdd(p.colsum + n1, accs[r]);
     }
-    const long long n1_0 = (tile / nt2) * 128, n2_0 = (tile % nt2) * 128;
-    const long long ms = split * p.rows_per_split;
-    long long me = ms + p.rows_per_split;
-    if (me > p.M) me = p.M;
-    if (ms >= me) return;
-    const int nst = (int)((me - ms) / TB_ROWS);                 // whole stages (checked on the host)
-
-    auto copy_stage = [&](int st) {                             // 8 copies per lane, counted in vmcnt
-        const long long m0 = ms + (long long)st * TB_ROWS;
-        unsigned char* base = tsm + (st % TB_NSTG) * TB_STG;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {                           // 16 chunks per row: 4 rows per wave instruction
-            const int row0 = (wave * 4 + i) * 4, row = row0 + (lane >> 4), c = (lane & 15) ^ tf_sw<16>(row);
-            tn_copy16(p.A + (m0 + row) * p.lda + n1_0 + c * 8, base + row0 * 256);
-            tn_copy16(p.B + (m0 + row) * p.ldb + n2_0 + c * 8, base + TB_ROWS * 256 + row0 * 256);
-        }
-    };
-    f32x16 acc[2][2], accs[2];
-#pragma unroll
-    for (int t = 0; t < 2; ++t) {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) { acc[t][0][r] = 0.0f; acc[t][1][r] = 0.0f; accs[t][r] = 0.0f; }
-    }
-    const bool do_cs = p.colsum != nullptr && (tile % nt2) == 0 && w2 == 0;
-    const bf16x8 ones = {0x3F80, 0x3F80, 0x3F80, 0x3F80, 0x3F80, 0x3F80, 0x3F80, 0x3F80};
-    const int grp = lane >> 4;
-#pragma unroll
-    for (int st = 0; st < TB_NSTG - 1; ++st)
-        if (st < nst) copy_stage(st);
-    for (int st = 0; st < nst; ++st) {
-        const int younger = nst - 1 - st;                       // stages st+1, st+2 may still fly (8 copies each)
-        if (younger >= 2) asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
-        else if (younger == 1) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        f_lds_barrier();                                        // stage st is in LDS, stage st-1 is released
-        if (st + TB_NSTG - 1 < nst) copy_stage(st + TB_NSTG - 1);
-        const unsigned char* sa = tsm + (st % TB_NSTG) * TB_STG;
-        const unsigned char* sb = sa + TB_ROWS * 256;
-        const bool cs_stage = do_cs && ms + (long long)st * TB_ROWS < p.cs_rows;
-        // fragments one k-step ahead of their MFMAs (one wave per SIMD: nobody else covers the LDS latency)
-        bf16x8 fa[2][2], fb[2][2];
-        auto frags = [&](int ks, bf16x8 (&a)[2], bf16x8 (&b)[2]) {
-            const int kbase = 16 * ks + 8 * (grp >> 1);
-#pragma unroll
-            for (int t = 0; t < 2; ++t) {
-                a[t] = tf_frag<16>(sa, kbase, w1 * 64 + 32 * t + 16 * (grp & 1), lane);
-                b[t] = tf_frag<16>(sb, kbase, w2 * 64 + 32 * t + 16 * (grp & 1), lane);
-            }
-        };
-        frags(0, fa[0], fb[0]);
-#pragma unroll
-        for (int ks = 0; ks < TB_ROWS / 16; ++ks) {
-            if (ks + 1 < TB_ROWS / 16) frags(ks + 1, fa[(ks + 1) & 1], fb[(ks + 1) & 1]);
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int t = 0; t < 2; ++t) {
-#pragma unroll
-                for (int u = 0; u < 2; ++u)
-                    acc[t][u] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[ks & 1][t], fb[ks & 1][u], acc[t][u], 0, 0, 0);
-                if (cs_stage) accs[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[ks & 1][t], ones, accs[t], 0, 0, 0);
-            }
-            __builtin_amdgcn_sched_barrier(0);
-        }
-    }
-#pragma unroll
-    for (int t = 0; t < 2; ++t)
-#pragma unroll
-        for (int u = 0; u < 2; ++u) {
-            const long long n2 = n2_0 + w2 * 64 + 32 * u + (lane & 31);
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const long long n1 = n1_0 + w1 * 64 + 32 * t + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-                atomicAdd(p.C + n1 * p.ldc + n2, acc[t][u][r]);
-                if (u == 0 && do_cs && (lane & 31) == 0) atomicAdd(p.colsum + n1, accs[t][r]);
-            }
-        }
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -1628,182 +1367,17 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_ws_kernel(GemmArgs p) {
 // ---------------------------------------------------------------------------------------------------------------
 // 256-feature layers of the training path (M x K -> M x 256, K = 128 or 256, bf16 in / bf16 out, optional bias, bf16
 // residual, activation): HBM-bound (A, the residual and C once each), so the kernel is built to keep the memory
-// system busy rather than the matrix pipe:
-//   * one persistent workgroup per CU (4 waves, 512 registers each); wave w holds the weight rows of feature slices
-//     w and w+4 for the whole launch (weight-stationary, 2*KS fragments);
-//   * 64-row tiles, two LDS images each for the operand rows and the residual rows.  The rows of tile i+1 travel
-//     global -> LDS without touching registers (global_load_lds_dwordx4) while tile i is computed; the swizzle is
-//     applied on the global side (lane p of a row fetches chunk p ^ (row & 15); its LDS slot is fixed by the lane);
-//   * the residual joins on the matrix pipe (two identity k-steps per slice against its LDS image), the bias seeds
-//     the accumulators; the epilogue packs to bf16 into an LDS image that the workgroup then streams out as whole
-//     512-byte rows;
-//   * barriers order LDS traffic only; the one vmcnt(0) per tile sits after the tile's MFMAs, where the copy issued
-//     before them has had the whole tile to land.
-// Measured anatomy at 65536 x 256 x 256 (no residual, 23 us): 10.8 us of data movement and synchronisation + 9 us of MFMA
-// phases + 7 us of store phases, simply added up -- one workgroup per CU runs its tile as a serial chain.  A 32-row /
-// two-workgroups-per-CU variant overlaps them (K = 128: 16.3 -> 14.1 us) but spills at K = 256 (128 weight registers in a
-// 256-register budget: 45 us); a third operand image and exact vmcnt accounting changed nothing.  Next step: split the
-// tile's phases across two wave groups of one workgroup.
-// LDS: 2 x 32 KB operand images + 2 x 32 KB residual images + 32 KB output image = 160 KB, 16-byte chunks XOR-swizzled
-// by row & 15 (conflict-free ds_read_b128 fragment reads).
-// ---------------------------------------------------------------------------------------------------------------
-constexpr int F_BM = 64, F_PITCH = 512, F_IMG = F_BM * F_PITCH;             // 32 768 bytes per image
-constexpr int F_LDS_BYTES = 5 * F_IMG;
-
-// MODE 0: plain, 1: + bf16 residual, 2: result * act'(dmask) (the layer's output feeds an activation backward)
-template <int KS, int MODE>
-__global__ __launch_bounds__(256, 1) void gemm_nt256_kernel(GemmArgs p) {
-    constexpr bool RES = MODE == 1, MASK = MODE == 2;
-    static_assert(KS == 8 || KS == 16, "K = 128 or 256");
-    constexpr int S = 2 * KS;                                                // 16-byte chunks per operand row
-    constexpr int XP = S * 16;                                               // operand image pitch (bytes)
-    constexpr int RCH = F_BM * 32 / 256;                                     // output chunks per thread
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    unsigned char* sX = smem;                                                // [2][F_IMG]
-    unsigned char* sR = smem + 2 * F_IMG;                                    // [2][F_IMG]
-    unsigned char* sO = smem + 4 * F_IMG;
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int r31 = lane & 31, h = lane >> 5, x = lane & 15;
-    const long long mtiles = p.M / F_BM, g = gridDim.x;
-
-    auto copy_tile = [&](long long mt, int buf) {                            // asynchronous: counted in vmcnt
-        const long long m0 = (mt < mtiles ? mt : mtiles - 1) * F_BM;         // tiles past the end re-read the last one
-        {
-            constexpr int RW = 1024 / XP;                                    // rows per wave instruction
-#pragma unroll
-            for (int i = 0; i < S / 4; ++i) {
-                const int row0 = (wave * (S / 4) + i) * RW, row = row0 + lane / S, c = (lane % S) ^ (row & 15);
-                f_copy16(p.A + (m0 + row) * p.lda + c * 8, sX + buf * F_IMG + row0 * XP);
-            }
-        }
-        if (RES || MASK) {                                       // the second image: residual rows or the mask source
-            const uint16_t* src = RES ? p.res : p.dmask;
-            const long long ld = RES ? p.ld_res : p.ld_dmask;
-#pragma unroll
-            for (int i = 0; i < 8; ++i) {
-                const int row0 = (wave * 8 + i) * 2, row = row0 + (lane >> 5), c = (lane & 31) ^ (row & 15);
-                f_copy16(src + (m0 + row) * ld + c * 8, sR + buf * F_IMG + row0 * F_PITCH);
-            }
-        }
-    };
-    long long mt = blockIdx.x;
-    if (mt >= mtiles) return;
-    copy_tile(mt, 0);
-    copy_tile(mt + g, 1);
-
-    bf16x8 wf[2][KS];
-    f32x16 seed[2];
-#pragma unroll
-    for (int t = 0; t < 2; ++t) {
-        const uint16_t* wrow = p.B + (long long)(32 * (wave + 4 * t) + r31) * p.ldb + 8 * h;
-#pragma unroll
-        for (int k = 0; k < KS; ++k) wf[t][k] = *reinterpret_cast<const bf16x8*>(wrow + 16 * k);
-#pragma unroll
-        for (int gq = 0; gq < 4; ++gq) {
-            f32x4 b4 = {0.f, 0.f, 0.f, 0.f};
-            if (p.bias != nullptr) b4 = *reinterpret_cast<const f32x4*>(p.bias + 32 * (wave + 4 * t) + 4 * h + 8 * gq);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) seed[t][4 * gq + e] = b4[e];
-        }
-    }
-    bf16x8 idf[2];                                                           // A[n][k'] = (n == 16 j + k'), k' = 8h + i
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-        const int dd = r31 - 16 * j - 8 * h;
-        unsigned v[4];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) v[q] = (dd == 2 * q ? 0x3F80u : 0u) | (dd == 2 * q + 1 ? 0x3F800000u : 0u);
-        const uint4 u = make_uint4(v[0], v[1], v[2], v[3]);
-        idf[j] = __builtin_bit_cast(bf16x8, u);
-    }
-    const float neg = p.act == DHAUG_ACT_RELU ? 0.0f : (p.act == DHAUG_ACT_LRELU ? p.slope : 1.0f);
-    const int lfx = r31 * XP | ((x >> 1) << 5) | ((h ^ (x & 1)) << 4);                   // ^ (k << 5): chunk 2k+h of row
-    const int lrx = (r31 * F_PITCH | ((x >> 1) << 5) | ((h ^ (x & 1)) << 4)) ^ (wave << 6);   // ^ (t << 8 | j << 5)
-    const int lep = r31 * F_PITCH | (((4 * wave) ^ x) << 4) | (h << 3);                  // ^ ((16t+g) << 4)
-    constexpr int XHALF = 32 * XP, HALF = 32 * F_PITCH;                                   // second 32-row half of an image
-
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    f_lds_barrier();
-    int buf = 0;
-    for (; mt < mtiles; mt += g, buf ^= 1) {
-        const unsigned char* X = sX + buf * F_IMG;
-        const unsigned char* R = sR + buf * F_IMG;
-        f32x16 acc[2][2];
-        bf16x8 fx[4];
-        constexpr int NST = 2 * KS, D = 3;                                   // (half, k) steps; fragment prefetch distance
-        auto fx_load = [&](int st) { fx[st & 3] = *reinterpret_cast<const bf16x8*>(X + (lfx ^ ((st % KS) << 5)) + (st / KS) * XHALF); };
-#pragma unroll
-        for (int st = 0; st < D; ++st) fx_load(st);
-#pragma unroll
-        for (int st = 0; st < NST; ++st) {
-            const int hf = st / KS, k = st % KS;
-            if (st + D < NST) fx_load(st + D);
-#pragma unroll
-            for (int t = 0; t < 2; ++t)
-                acc[hf][t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf[t][k], fx[st & 3], k == 0 ? seed[t] : acc[hf][t], 0, 0, 0);
-        }
-        if (RES) {
-#pragma unroll
-            for (int hf = 0; hf < 2; ++hf)
-#pragma unroll
-                for (int j = 0; j < 2; ++j)
-#pragma unroll
-                    for (int t = 0; t < 2; ++t) {
-                        const bf16x8 rf = *reinterpret_cast<const bf16x8*>(R + (lrx ^ (t << 8 | j << 5)) + hf * HALF);
-                        acc[hf][t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(idf[j], rf, acc[hf][t], 0, 0, 0);
-                    }
-        }
-        // epilogue -> output image
-#pragma unroll
-        for (int hf = 0; hf < 2; ++hf)
-#pragma unroll
-            for (int t = 0; t < 2; ++t)
-#pragma unroll
-                for (int gq = 0; gq < 4; ++gq) {
-                    float v[4];
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        const float a = acc[hf][t][4 * gq + e];
-                        v[e] = fmaxf(a, a * neg);
-                    }
-                    if (MASK) {                                              // this lane's 4 mask-source values (bf16)
-                        const uint2 y = *reinterpret_cast<const uint2*>(R + (lep ^ ((16 * t + gq) << 4)) + hf * HALF);
-                        const short y0 = (short)(y.x & 0xffffu), y1 = (short)(y.x >> 16), y2 = (short)(y.y & 0xffffu), y3 = (short)(y.y >> 16);
-                        v[0] = y0 > 0 ? v[0] : v[0] * p.dneg;                // a positive bf16 is a positive int16
-                        v[1] = y1 > 0 ? v[1] : v[1] * p.dneg;
-                        v[2] = y2 > 0 ? v[2] : v[2] * p.dneg;
-                        v[3] = y3 > 0 ? v[3] : v[3] * p.dneg;
-                    }
-                    uint2 o;
-                    o.x = f_pack_bf16x2(v[0], v[1]);
-                    o.y = f_pack_bf16x2(v[2], v[3]);
-                    *reinterpret_cast<uint2*>(sO + (lep ^ ((16 * t + gq) << 4)) + hf * HALF) = o;
-                }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                   // the next tile's rows have landed
-        f_lds_barrier();                                                     // output image complete; image buf is free
-        typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-        u32x4 o[RCH];
-#pragma unroll
-        for (int i = 0; i < RCH; ++i) {
-            const int q = tid + 256 * i, row = q >> 5, c = q & 31;
-            o[i] = *reinterpret_cast<const u32x4*>(sO + row * F_PITCH + ((c ^ (row & 15)) << 4));
-        }
-        copy_tile(mt + 2 * g, buf);
-        f_lds_barrier();                                                     // output image free again
-        const long long m0 = mt * F_BM;
-#pragma unroll
-        for (int i = 0; i < RCH; ++i) {
-            const int q = tid + 256 * i, row = q >> 5, c = q & 31;
-            *reinterpret_cast<u32x4*>(p.cb + (m0 + row) * p.ldcb + c * 8) = o[i];
-        }
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                       // no copy may land in LDS after the workgroup is gone
-}
-
-// ---------------------------------------------------------------------------------------------------------------
-// The same layer with the tile's serial chain cut in two (gemm_nt256_kernel above: 10.8 us of movement + 9 us of MFMA
-// phases + 7 us of store phases, added up).  512 threads, two roles, one LDS-only barrier per 32-row tile:
+// system busy rather than the matrix pipe.  Weight-stationary (a compute wave holds the weight rows of two feature slices
+// for the whole launch); the rows of the tiles ahead travel global -> LDS without touching registers
+// (global_load_lds_dwordx4), the swizzle applied on the global side (lane p of a row fetches chunk p ^ (row & 15); its LDS
+// slot is fixed by the lane); the residual joins on the matrix pipe (two identity k-steps per slice against its LDS image);
+// the epilogue packs to bf16 into an LDS image that is streamed out as whole 512-byte rows; barriers order LDS traffic only.
+// The first version (retired) ran this as one persistent 256-thread workgroup per CU on 64-row tiles, every wave doing every
+// phase.  Measured anatomy at 65536 x 256 x 256 (no residual, 23 us): 10.8 us of data movement and synchronisation + 9 us of
+// MFMA phases + 7 us of store phases, simply added up -- one workgroup per CU ran its tile as a serial chain.  A 32-row /
+// two-workgroups-per-CU variant overlapped them (K = 128: 16.3 -> 14.1 us) but spilled at K = 256 (128 weight registers in a
+// 256-register budget: 45 us); a third operand image and exact vmcnt accounting changed nothing.
+// Here the tile's serial chain is cut in two: 512 threads, two roles, one LDS-only barrier per 32-row tile:
 //   waves 0..3 (compute): MFMAs of tile i from its LDS images, epilogue (bias from an LDS copy, residual on the matrix
 //                         pipe, activation, mask), bf16 result into output image i % 2;
 //   waves 4..7 (movers) : request tile i+NX-1's rows into the image tile i-1 released (global_load_lds_dwordx4), stream
@@ -1811,8 +1385,11 @@ __global__ __launch_bounds__(256, 1) void gemm_nt256_kernel(GemmArgs p) {
 //                         the barrier.
 // Two waves per SIMD: 256 registers each, so a compute wave keeps the weights (2 * KS fragments = 128 registers at
 // K = 256) but no bias seeds.  Tile j lives in operand image j % NX (NX = 4 without a second operand, 3 with one).
-// LDS: NX (x2 with a second operand) images of 16 KB + two output images + bias 1 KB = 97 / 129 KB.
+// LDS: NX (x2 with a second operand) images of 16 KB + two output images + bias 1 KB = 97 / 129 KB, 16-byte chunks
+// XOR-swizzled by row & 15 (conflict-free ds_read_b128 fragment reads).
+// The batch must be whole 64-row tiles (F_BM, dhaug_gemm_route.h).
 // ---------------------------------------------------------------------------------------------------------------
+constexpr int F_PITCH = 512;                                                // bytes per image row
 // MODE bit 0: residual, bit 1: activation-backward mask; both (3): (A B^T + res) * act'(mask), the input-gradient step of a
 // residual block (gz1 W1 + gz2) * relu'(x) and its tangent twin -- three operand streams, so the ring holds 2 tiles
 template <int KS, int MODE>
@@ -1854,20 +1431,20 @@ __global__ __launch_bounds__(512, 1) void gemm_nt256s_kernel(GemmArgs p) {
 #pragma unroll
             for (int q = 0; q < NCX; ++q) {
                 const int row0 = (cw * NCX + q) * RW, row = row0 + lane / S, c = (lane % S) ^ (row & 15);
-                f_copy16(p.A + (m0 + row) * p.lda + c * 8, sX + buf * IMG + row0 * XP);
+                p_copy16(p.A + (m0 + row) * p.lda + c * 8, sX + buf * IMG + row0 * XP);
             }
             if (RES) {
 #pragma unroll
                 for (int q = 0; q < NCR1; ++q) {
                     const int row0 = (cw * NCR1 + q) * 2, row = row0 + (lane >> 5), c = (lane & 31) ^ (row & 15);
-                    f_copy16(p.res + (m0 + row) * p.ld_res + c * 8, sR + buf * IMG + row0 * F_PITCH);
+                    p_copy16(p.res + (m0 + row) * p.ld_res + c * 8, sR + buf * IMG + row0 * F_PITCH);
                 }
             }
             if (MASK) {
 #pragma unroll
                 for (int q = 0; q < NCR1; ++q) {
                     const int row0 = (cw * NCR1 + q) * 2, row = row0 + (lane >> 5), c = (lane & 31) ^ (row & 15);
-                    f_copy16(p.dmask + (m0 + row) * p.ld_dmask + c * 8, sM + buf * IMG + row0 * F_PITCH);
+                    p_copy16(p.dmask + (m0 + row) * p.ld_dmask + c * 8, sM + buf * IMG + row0 * F_PITCH);
                 }
             }
         };
@@ -1880,7 +1457,7 @@ __global__ __launch_bounds__(512, 1) void gemm_nt256s_kernel(GemmArgs p) {
         }
         if (nt >= NX - 1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"((NX - 2) * (NCX + NCR)) : "memory");   // tile 0 landed
         else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        f_lds_barrier();
+        p_lds_barrier();
         typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
         const int mtid = tid - 256;
         for (int i = 0; i <= nt; ++i) {                                      // iteration i: tile i is being computed
@@ -1912,7 +1489,7 @@ __global__ __launch_bounds__(512, 1) void gemm_nt256s_kernel(GemmArgs p) {
             else if (ks == 1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"((NX - 2) * (NCX + NCR) + RCH) : "memory");
             else if (ks == 2) asm volatile("s_waitcnt vmcnt(%0)" ::"n"((NX - 2) * (NCX + NCR) + 2 * RCH) : "memory");
             else asm volatile("s_waitcnt vmcnt(%0)" ::"n"((NX - 2) * (NCX + NCR) + 3 * RCH) : "memory");
-            f_lds_barrier();
+            p_lds_barrier();
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         return;
@@ -1945,7 +1522,7 @@ __global__ __launch_bounds__(512, 1) void gemm_nt256s_kernel(GemmArgs p) {
     const f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     // sign bits of this wave's two slices for the lane's row of tile j: word ((tile * 4 + cw) * 64 + lane), one tile ahead
     uint32_t bw_next = BITS ? p.dbits[((mt0 * 4) + cw) * 64 + lane] : 0u;
-    f_lds_barrier();                                                         // tile 0 and the bias are in LDS
+    p_lds_barrier();                                                         // tile 0 and the bias are in LDS
     for (int i = 0; i < nt; ++i) {
         const unsigned char* X = sX + (i % NX) * IMG;
         const unsigned char* R = sR + (i % NX) * IMG;
@@ -2014,7 +1591,7 @@ __global__ __launch_bounds__(512, 1) void gemm_nt256s_kernel(GemmArgs p) {
                                                                              __builtin_bit_cast(s16x2, lb)));
                 *reinterpret_cast<uint2*>(O + (lep ^ ((16 * t + gq) << 4))) = o;
             }
-        f_lds_barrier();                                                     // output image i complete, operand image i released
+        p_lds_barrier();                                                     // output image i complete, operand image i released
     }
 }
 
@@ -2131,21 +1708,21 @@ __global__ __launch_bounds__(512, 1) void gemm_block2_kernel(Block2Args p) {
         }
         if (ws == 0 && blk > 0) asm volatile("s_waitcnt vmcnt(0)\n\tbuffer_inv sc1" ::: "memory");   // (+ the previous block's row stores)
         else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        f_lds_barrier();
+        p_lds_barrier();
         if ((ws == 1) == stageB) {
 #pragma unroll
             for (int t = 0; t < 2; ++t)
 #pragma unroll
                 for (int k = 0; k < 16; ++k) wf[t][k] = *reinterpret_cast<const bf16x8*>(smem + 32 * (cw + 4 * t) * F_PITCH + (lfx ^ (k << 5)));
         }
-        f_lds_barrier();                                                     // (fragments in registers: the area is free again)
+        p_lds_barrier();                                                     // (fragments in registers: the area is free again)
     }
     if (0 < nt) copy_tile(0);
     if (1 < nt) copy_tile(1);
     B2_STAMP(1)
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     B2_STAMP(2)
-    f_lds_barrier();                                                         // tiles 0 and 1 are in LDS
+    p_lds_barrier();                                                         // tiles 0 and 1 are in LDS
     B2_STAMP(3)
 
     for (int i = 0; i <= nt + 1; ++i) {
@@ -2272,7 +1849,7 @@ __global__ __launch_bounds__(512, 1) void gemm_block2_kernel(Block2Args p) {
             default: break;
         }
         B2_STAMP(13 + 8 * i)
-        f_lds_barrier();
+        p_lds_barrier();
         B2_STAMP(14 + 8 * i)
     }
     B2_STAMP(4)
@@ -2280,7 +1857,7 @@ __global__ __launch_bounds__(512, 1) void gemm_block2_kernel(Block2Args p) {
     // (the rows this workgroup stored are the next block's operand: their drain -- and the L1 invalidate -- waits behind the next
     // block's first weight copy; the last block's stores are completed by the end of the kernel)
     B2_STAMP(5)
-    f_lds_barrier();                                                         // every image is free
+    p_lds_barrier();                                                         // every image is free
     B2_STAMP(6)
     }
 }
@@ -2290,13 +1867,7 @@ int launch_nt256s_mode(hipStream_t s, const GemmArgs& p) {
     constexpr int NSEC = (MODE & 1) + ((MODE >> 1) & 1);                   // (bit 2, the sign-bit mask, has no image)
     constexpr int BM = 32, NX = 4 - NSEC;
     constexpr int LDS = ((1 + NSEC) * NX + 2) * BM * F_PITCH + 1024;
-    static bool configured = false;
-    if (!configured) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_nt256s_kernel<KS, MODE>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-        if (e != hipSuccess) return (int)e;
-        configured = true;
-    }
+    if (const int rc = dhaug_dynamic_lds<gemm_nt256s_kernel<KS, MODE>>(LDS)) return rc;
     const long long mtiles = p.M / BM;
     const unsigned grid = dhaug_persistent_grid(mtiles);
     hipLaunchKernelGGL((gemm_nt256s_kernel<KS, MODE>), dim3(grid), dim3(512), LDS, s, p);
@@ -2314,38 +1885,9 @@ int launch_nt256s(hipStream_t s, const GemmArgs& p) {
     return launch_nt256s_mode<KS, 0>(s, p);
 }
 
-template <int KS>
-int launch_nt256(hipStream_t s, const GemmArgs& p) {
-    static bool configured = false;
-    if (!configured) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_nt256_kernel<KS, 0>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, F_LDS_BYTES);
-        if (e == hipSuccess)
-            e = hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_nt256_kernel<KS, 1>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, F_LDS_BYTES);
-        if (e == hipSuccess)
-            e = hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_nt256_kernel<KS, 2>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, F_LDS_BYTES);
-        if (e != hipSuccess) return (int)e;
-        configured = true;
-    }
-    const long long mtiles = p.M / F_BM;
-    const unsigned grid = dhaug_persistent_grid(mtiles);
-    if (p.dmask != nullptr) hipLaunchKernelGGL((gemm_nt256_kernel<KS, 2>), dim3(grid), dim3(256), F_LDS_BYTES, s, p);
-    else if (p.res != nullptr) hipLaunchKernelGGL((gemm_nt256_kernel<KS, 1>), dim3(grid), dim3(256), F_LDS_BYTES, s, p);
-    else hipLaunchKernelGGL((gemm_nt256_kernel<KS, 0>), dim3(grid), dim3(256), F_LDS_BYTES, s, p);
-    return dhaug_launch_status();
-}
-
 template <int KSTEPS>
 int launch_ws(hipStream_t s, const GemmArgs& p) {
-    static bool configured = false;
-    if (!configured) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_nt_ws_kernel<KSTEPS>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, 2 * WS_BUF_BYTES);
-        if (e != hipSuccess) return (int)e;
-        configured = true;
-    }
+    if (const int rc = dhaug_dynamic_lds<gemm_nt_ws_kernel<KSTEPS>>(2 * WS_BUF_BYTES)) return rc;
     const long long ntiles = (p.W + WS_BN - 1) / WS_BN, mtiles = (p.M + WS_BM - 1) / WS_BM;
     long long gx = 2 * (long long)dhaug_persistent_grid(256) / ntiles;          // two workgroups per CU
     if (gx < 1) gx = 1;
@@ -2354,40 +1896,59 @@ int launch_ws(hipStream_t s, const GemmArgs& p) {
     return dhaug_launch_status();
 }
 
-template <typename Kern>
-int launch_nt(Kern kern, long long grid, size_t lds, hipStream_t s, const GemmArgs& p) {
-    static bool configured = false;          // one attribute call per kernel instantiation
-    if (!configured) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return (int)e;
-        configured = true;
+// the weight-stationary kernel's instantiations, by K / 16
+int launch_ws_ksteps(int ksteps, hipStream_t s, const GemmArgs& p) {
+    switch (ksteps) {
+        case 1: return launch_ws<1>(s, p);
+        case 2: return launch_ws<2>(s, p);
+        case 3: return launch_ws<3>(s, p);
+        case 4: return launch_ws<4>(s, p);
+        case 7: return launch_ws<7>(s, p);
+        case 8: return launch_ws<8>(s, p);
+        case 16: return launch_ws<16>(s, p);
+        default: return DHAUG_EUNSUPPORTED;
     }
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(256), lds, s, p);
+}
+
+// gemm_nt_kernel on BM x BN tiles
+template <int BM, int BN, int WAVES_M, int WAVES_N>
+int launch_generic(hipStream_t s, const GemmArgs& p) {
+    constexpr int stages = 2 * (BM + BN) * BK * 2, ctile = BM * (BN + 4) * 4;
+    constexpr int lds = stages > ctile ? stages : ctile;
+    if (const int rc = dhaug_dynamic_lds<gemm_nt_kernel<BM, BN, WAVES_M, WAVES_N>>(lds)) return rc;
+    const long long grid = ((p.M + BM - 1) / BM) * ((p.W + BN - 1) / BN);
+    hipLaunchKernelGGL((gemm_nt_kernel<BM, BN, WAVES_M, WAVES_N>), dim3((unsigned)grid), dim3(256), lds, s, p);
     return dhaug_launch_status();
 }
 
-}  // namespace
-
-extern "C" {
-
-static int launch_wide(hipStream_t s, const GemmArgs& p) {
-    static bool configured = false;
-    if (!configured) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_nt_wide_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, W_LDS);
-        if (e != hipSuccess) return (int)e;
-        configured = true;
-    }
+int launch_wide(hipStream_t s, const GemmArgs& p) {
+    if (const int rc = dhaug_dynamic_lds<gemm_nt_wide_kernel>(W_LDS)) return rc;
     const long long grid = (((p.M + W_BM - 1) / W_BM + 7) / 8 * 8) * ((p.W + W_BN - 1) / W_BN);     // (row blocks padded to eight: XCD map)
     hipLaunchKernelGGL(gemm_nt_wide_kernel, dim3((unsigned)grid), dim3(512), W_LDS, s, p);
     return dhaug_launch_status();
 }
 
-static int gemm_bf16_impl(const uint16_t* A, int64_t lda, const uint16_t* B, int64_t ldb, const float* bias,
-                          const uint16_t* residual, int64_t ld_res, const float* residual_f32, int64_t ld_res_f32,
-                          uint16_t* c_bf16, int64_t ldc_bf16, int64_t n_pad_zero,
-                          float* c_f32, int64_t ldc_f32, int64_t M, int64_t N, int64_t K, int act, float slope,
-                          const uint16_t* dmask, int64_t ld_dmask, float dneg, bool* mask_done, void* stream,
-                          const float* dmaskf = nullptr, int64_t ld_dmaskf = 0, GemmArgs* collect = nullptr) {
+int launch_big(hipStream_t s, const GemmArgs& p) {
+    if (const int rc = dhaug_dynamic_lds<gemm_nt_big_kernel>(G_LDS)) return rc;
+    const long long grid = ((p.M + G_BM - 1) / G_BM) * ((p.W + G_BN - 1) / G_BN);
+    hipLaunchKernelGGL(gemm_nt_big_kernel, dim3((unsigned)grid), dim3(256), G_LDS, s, p);
+    return dhaug_launch_status();
+}
+
+int launch_pipe2(hipStream_t s, const GemmArgs& p) {
+    const long long grid = ((p.M + 63) / 64) * ((p.W + 63) / 64);
+    hipLaunchKernelGGL(gemm_nt_pipe2_kernel, dim3((unsigned)grid), dim3(256), 4 * (64 + 64) * BK * 2, s, p);
+    return dhaug_launch_status();
+}
+
+// Validate, fill the arguments, route (dhaug_gemm_route.h), launch.  `collect`: a member of a group (dhaug_gemm_bf16_group) is
+// checked and returned, not launched.
+int gemm_bf16_impl(const uint16_t* A, int64_t lda, const uint16_t* B, int64_t ldb, const float* bias,
+                   const uint16_t* residual, int64_t ld_res, const float* residual_f32, int64_t ld_res_f32,
+                   uint16_t* c_bf16, int64_t ldc_bf16, int64_t n_pad_zero,
+                   float* c_f32, int64_t ldc_f32, int64_t M, int64_t N, int64_t K, int act, float slope,
+                   const uint16_t* dmask, int64_t ld_dmask, float dneg, void* stream,
+                   const float* dmaskf = nullptr, int64_t ld_dmaskf = 0, GemmArgs* collect = nullptr) {
     DHAUG_CHECK(M >= 0 && N >= 1 && K >= 16, DHAUG_EINVAL);
     DHAUG_CHECK(act >= DHAUG_ACT_NONE && act <= DHAUG_ACT_LRELU, DHAUG_EINVAL);
     if (M == 0) return DHAUG_OK;
@@ -2403,119 +1964,55 @@ static int gemm_bf16_impl(const uint16_t* A, int64_t lda, const uint16_t* B, int
     GemmArgs p{A, lda, B, ldb, bias, residual, ld_res, residual_f32, ld_res_f32, c_bf16, ldc_bf16, c_bf16 ? (n_pad_zero > N ? n_pad_zero : N) : 0,
                c_f32, ldc_f32, M, N, K, N, act, slope, nullptr, 0, 1.0f, nullptr, nullptr, 0};
     hipStream_t s = (hipStream_t)stream;
-    const long long width = (c_bf16 && p.npad > N) ? p.npad : N;
-    p.W = width;
-    if (collect != nullptr) {                                    // a member of a group (dhaug_gemm_bf16_group): checked, not launched
-        DHAUG_CHECK(M > 0 && width > 64 && K >= 64 && lda >= 64 && ldb >= 64 && dmaskf == nullptr, DHAUG_EUNSUPPORTED);
-        if (dmask != nullptr) { p.dmask = dmask; p.ld_dmask = ld_dmask; p.dneg = dneg; *mask_done = true; }
+    p.W = (c_bf16 && p.npad > N) ? p.npad : N;
+    // the activation-backward mask, bf16 or fp32 values (fp32: the kernels whose epilogue is nt_store_tile, and p8)
+    if (dmaskf != nullptr) {
+        DHAUG_CHECK(dmask == nullptr && ld_dmaskf >= N, DHAUG_EINVAL);
+        p.dmaskf = dmaskf; p.ld_dmaskf = ld_dmaskf; p.dneg = dneg;
+    } else if (dmask != nullptr) {
+        p.dmask = dmask; p.ld_dmask = ld_dmask; p.dneg = dneg;
+    }
+    if (collect != nullptr) {
+        DHAUG_CHECK(p.W > 64 && K >= 64 && lda >= 64 && ldb >= 64 && dmaskf == nullptr, DHAUG_EUNSUPPORTED);
         *collect = p;
         return DHAUG_OK;
     }
-    if (dmaskf != nullptr) {                                     // (fp32 mask: applied by nt_store_tile -- the kernels that have it)
-        DHAUG_CHECK(dmask == nullptr && ld_dmaskf >= N, DHAUG_EINVAL);
-        p.dmaskf = dmaskf; p.ld_dmaskf = ld_dmaskf; p.dneg = dneg;
+    // (DHAUG_GEMM_WIDE_MIN_TILES: a test switch -- the golden-vector tests reach the 256 x 256-tile kernels with a few hundred rows;
+    // the other three take a kernel out of the choice, for cross-checks against its successor in line)
+    const char* min_tiles = getenv("DHAUG_GEMM_WIDE_MIN_TILES");
+    const NtShape shape{M, N, p.W, K, c_bf16 != nullptr, c_f32 != nullptr, residual_f32 != nullptr, bias == nullptr || dhaug_aligned16(bias),
+                        dmaskf != nullptr, dhaug_p8_supported(p),
+                        getenv("DHAUG_GEMM_NO256") != nullptr, getenv("DHAUG_GEMM_NOBIG") != nullptr, getenv("DHAUG_GEMM_NOP8") != nullptr,
+                        min_tiles ? atoll(min_tiles) : WIDE_MIN_TILES_DEFAULT};
+    const NtRoute r = nt_route(shape);
+    switch (r.kernel) {
+        case NT256S:
+            // the one kernel that does not apply the mask in a coalesced epilogue: it copies the mask rows into an LDS image of
+            // their own, in 16-byte chunks
+            if (dmask != nullptr) DHAUG_CHECK(ld_dmask % 8 == 0 && dhaug_aligned16(dmask), DHAUG_EALIGN);
+            return r.ksteps == 8 ? launch_nt256s<8>(s, p) : launch_nt256s<16>(s, p);
+        case WS: return launch_ws_ksteps(r.ksteps, s, p);
+        case P8: return dhaug_p8_launch(s, p);
+        case WIDE: p.abl = DHAUG_ABL_ENV("DHAUG_BIG_ABL"); return launch_wide(s, p);       // (development: timing only)
+        case BIG: p.abl = DHAUG_ABL_ENV("DHAUG_BIG_ABL"); return launch_big(s, p);
+        case PIPE2: return launch_pipe2(s, p);
+        case GENERIC_128x128: return launch_generic<128, 128, 2, 2>(s, p);
+        case GENERIC_128x64: return launch_generic<128, 64, 2, 2>(s, p);
+        case GENERIC_128x32: return launch_generic<128, 32, 4, 1>(s, p);
     }
-    // the training path's 256-wide layers
-    if (dmaskf == nullptr && N == 256 && width == 256 && K <= 256 && M % F_BM == 0 && c_bf16 != nullptr && c_f32 == nullptr && residual_f32 == nullptr &&
-        (bias == nullptr || dhaug_aligned16(bias)) && getenv("DHAUG_GEMM_GENERIC") == nullptr && getenv("DHAUG_GEMM_NO256") == nullptr) {
-        if (getenv("DHAUG_NT256_SINGLE") == nullptr) {                        // two-role kernel (default): mask in its own LDS image
-            if (dmask != nullptr && (K == 128 || K == 256)) {
-                DHAUG_CHECK(ld_dmask % 8 == 0 && dhaug_aligned16(dmask), DHAUG_EALIGN);
-                p.dmask = dmask; p.ld_dmask = ld_dmask; p.dneg = dneg;
-                *mask_done = true;
-            }
-            if (K == 128) return launch_nt256s<8>(s, p);
-            if (K == 256) return launch_nt256s<16>(s, p);
-        } else if (dmask == nullptr || residual == nullptr) {                 // single-role kernel: mask OR residual
-            if (dmask != nullptr && (K == 128 || K == 256)) {
-                p.dmask = dmask; p.ld_dmask = ld_dmask; p.dneg = dneg;
-                *mask_done = true;
-            }
-            switch (K / 16) {
-                case 8: return launch_nt256<8>(s, p);
-                case 16: return launch_nt256<16>(s, p);
-                default: break;
-            }
-        }
-    }
-    // every other kernel applies the mask in its coalesced epilogue
-    if (dmask != nullptr && !*mask_done) {
-        p.dmask = dmask; p.ld_dmask = ld_dmask; p.dneg = dneg;
-        *mask_done = true;
-    }
-    if (dmaskf == nullptr && width > 64 && K <= 256 && getenv("DHAUG_GEMM_GENERIC") == nullptr) {
-        switch (K / 16) {
-            case 1: return launch_ws<1>(s, p);
-            case 2: return launch_ws<2>(s, p);
-            case 3: return launch_ws<3>(s, p);
-            case 4: return launch_ws<4>(s, p);
-            case 7: return launch_ws<7>(s, p);
-            case 8: return launch_ws<8>(s, p);
-            case 16: return launch_ws<16>(s, p);
-            default: break;
-        }
-    }
-    // (DHAUG_GEMM_WIDE_MIN_TILES: a test switch -- the golden-vector tests reach these kernels with a few hundred rows)
-    const long long wide_min_tiles = getenv("DHAUG_GEMM_WIDE_MIN_TILES") ? atoll(getenv("DHAUG_GEMM_WIDE_MIN_TILES")) : 160;
-    if (width >= 256 && ((M + W_BM - 1) / W_BM) * ((width + W_BN - 1) / W_BN) >= wide_min_tiles && K >= 64 && lda >= 64 && ldb >= 64 &&
-        getenv("DHAUG_GEMM_NOWIDE") == nullptr && getenv("DHAUG_GEMM_NOBIG") == nullptr && getenv("DHAUG_GEMM_NOPIPE") == nullptr) {
-        // long batch, tiles enough for most of the card: 256 x 256 tiles, eight waves (the DenseDim-1000 layers of the frame
-        // critics; the 256-wide layers of the split-operand parity arithmetic, K' = 3 K or 6 K)
-        // (since round 6: the ping-pong kernel of dhaug_gemm_p8.hip; DHAUG_GEMM_NOP8=1 keeps the five-stage kernel below)
-        if (getenv("DHAUG_GEMM_NOP8") == nullptr && dhaug_p8_supported(p)) return dhaug_p8_launch(s, p);
-        p.abl = DHAUG_ABL_ENV("DHAUG_BIG_ABL");   // (development: timing only)
-        return launch_wide(s, p);
-    }
-    if (width >= 512 && M >= 4096 && K >= 64 && lda >= 64 && ldb >= 64 && getenv("DHAUG_GEMM_NOBIG") == nullptr &&
-        getenv("DHAUG_GEMM_NOPIPE") == nullptr) {
-        // long batch, wide layer: 128 x 256 tiles, 64 x 128 per wave
-        static bool configured = false;
-        if (!configured) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_nt_big_kernel),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, G_LDS);
-            if (e != hipSuccess) return (int)e;
-            configured = true;
-        }
-        const long long grid = ((M + G_BM - 1) / G_BM) * ((width + G_BN - 1) / G_BN);
-        p.abl = DHAUG_ABL_ENV("DHAUG_BIG_ABL");
-        hipLaunchKernelGGL(gemm_nt_big_kernel, dim3((unsigned)grid), dim3(256), G_LDS, s, p);
-        return dhaug_launch_status();
-    }
-    if (width > 64 && K >= 64 && lda >= 64 && ldb >= 64 && getenv("DHAUG_GEMM_NOPIPE") == nullptr) {
-        const long long grid = ((M + 63) / 64) * ((width + 63) / 64);
-        p.abl = DHAUG_ABL_ENV("DHAUG_BIG_ABL");   // (development: timing only)
-        if (getenv("DHAUG_GEMM_PIPE1") == nullptr) {
-            hipLaunchKernelGGL(gemm_nt_pipe2_kernel, dim3((unsigned)grid), dim3(256), 4 * (64 + 64) * BK * 2, s, p);
-            return dhaug_launch_status();
-        }
-        hipLaunchKernelGGL((gemm_nt_pipe_kernel<64, 4>), dim3((unsigned)grid), dim3(256), 4 * (64 + 64) * BK * 2, s, p);
-        return dhaug_launch_status();
-    }
-    if (width > 64) {
-        constexpr int BM = 128, BN = 128;
-        const long long grid = ((M + BM - 1) / BM) * ((width + BN - 1) / BN);
-        size_t lds = (size_t)2 * (BM + BN) * BK * 2, ctile = (size_t)BM * (BN + 4) * 4;
-        return launch_nt(gemm_nt_kernel<BM, BN, 2, 2>, grid, lds > ctile ? lds : ctile, s, p);
-    } else if (width > 32) {
-        constexpr int BM = 128, BN = 64;
-        const long long grid = ((M + BM - 1) / BM);
-        size_t lds = (size_t)2 * (BM + BN) * BK * 2, ctile = (size_t)BM * (BN + 4) * 4;
-        return launch_nt(gemm_nt_kernel<BM, BN, 2, 2>, grid, lds > ctile ? lds : ctile, s, p);
-    } else {
-        constexpr int BM = 128, BN = 32;
-        const long long grid = ((M + BM - 1) / BM);
-        size_t lds = (size_t)2 * (BM + BN) * BK * 2, ctile = (size_t)BM * (BN + 4) * 4;
-        return launch_nt(gemm_nt_kernel<BM, BN, 4, 1>, grid, lds > ctile ? lds : ctile, s, p);
-    }
+    return DHAUG_EINVAL;
 }
+
+}  // namespace
+
+extern "C" {
 
 int dhaug_gemm_bf16(const uint16_t* A, int64_t lda, const uint16_t* B, int64_t ldb, const float* bias,
                     const uint16_t* residual, int64_t ld_res, const float* residual_f32, int64_t ld_res_f32,
                     uint16_t* c_bf16, int64_t ldc_bf16, int64_t n_pad_zero,
                     float* c_f32, int64_t ldc_f32, int64_t M, int64_t N, int64_t K, int act, float slope, void* stream) {
-    bool done = false;
     return gemm_bf16_impl(A, lda, B, ldb, bias, residual, ld_res, residual_f32, ld_res_f32, c_bf16, ldc_bf16, n_pad_zero, c_f32,
-                          ldc_f32, M, N, K, act, slope, nullptr, 0, 1.0f, &done, stream);
+                          ldc_f32, M, N, K, act, slope, nullptr, 0, 1.0f, stream);
 }
 
 /* see include/dhaug.h */
@@ -2599,9 +2096,8 @@ int dhaug_gemm_bf16_dmask_pad(const uint16_t* A, int64_t lda, const uint16_t* B,
     if (dmask_act == DHAUG_ACT_NONE) dmask = nullptr;
     if (dmask) DHAUG_CHECK(ld_dmask >= N && (reinterpret_cast<uintptr_t>(dmask) & 1u) == 0, DHAUG_EALIGN);
     const float dneg = dmask_act == DHAUG_ACT_RELU ? 0.0f : dmask_slope;
-    bool done = false;
     return gemm_bf16_impl(A, lda, B, ldb, nullptr, residual, ld_res, nullptr, 0, c_bf16, ldc_bf16, n_pad_zero > N ? n_pad_zero : N,
-                          nullptr, 0, M, N, K, DHAUG_ACT_NONE, 0.0f, dmask, ld_dmask, dneg, &done, stream);
+                          nullptr, 0, M, N, K, DHAUG_ACT_NONE, 0.0f, dmask, ld_dmask, dneg, stream);
 }
 
 /* see include/dhaug.h */
@@ -2615,10 +2111,9 @@ int dhaug_gemm_bf16_group(const dhaug_gemm_desc* d, int n, void* stream) {
         DHAUG_CHECK(e.dmask_act >= DHAUG_ACT_NONE && e.dmask_act <= DHAUG_ACT_LRELU, DHAUG_EINVAL);
         const uint16_t* dm = e.dmask_act == DHAUG_ACT_NONE ? nullptr : e.dmask;
         if (dm) DHAUG_CHECK(e.ld_dmask >= e.N && (reinterpret_cast<uintptr_t>(dm) & 1u) == 0, DHAUG_EALIGN);
-        bool done = false;
         const int rc = gemm_bf16_impl(e.A, e.lda, e.B, e.ldb, e.bias, e.residual, e.ld_res, e.residual_f32, e.ld_res_f32, e.c_bf16,
                                       e.ldc_bf16, e.n_pad_zero, e.c_f32, e.ldc_f32, e.M, e.N, e.K, e.act, e.slope, dm, e.ld_dmask,
-                                      e.dmask_act == DHAUG_ACT_RELU ? 0.0f : e.dmask_slope, &done, stream, nullptr, 0, &ga.g[i]);
+                                      e.dmask_act == DHAUG_ACT_RELU ? 0.0f : e.dmask_slope, stream, nullptr, 0, &ga.g[i]);
         if (rc != DHAUG_OK) return rc;
         DHAUG_CHECK(ga.g[i].W == ga.g[0].W, DHAUG_EUNSUPPORTED);
     }
@@ -2657,9 +2152,8 @@ int dhaug_gemm_bf16_dmask_f32(const uint16_t* A, int64_t lda, const uint16_t* B,
                               int64_t M, int64_t N, int64_t K, void* stream) {
     DHAUG_CHECK(dmask_act == DHAUG_ACT_RELU || dmask_act == DHAUG_ACT_LRELU, DHAUG_EINVAL);
     DHAUG_CHECK_PTR(c_f32); DHAUG_CHECK_PTR(dmask);
-    bool done = false;
     return gemm_bf16_impl(A, lda, B, ldb, nullptr, nullptr, 0, residual_f32, ld_res_f32, nullptr, 0, 0, c_f32, ldc_f32, M, N, K,
-                          DHAUG_ACT_NONE, 0.0f, nullptr, 0, dmask_act == DHAUG_ACT_RELU ? 0.0f : dmask_slope, &done, stream, dmask, ld_dmask);
+                          DHAUG_ACT_NONE, 0.0f, nullptr, 0, dmask_act == DHAUG_ACT_RELU ? 0.0f : dmask_slope, stream, dmask, ld_dmask);
 }
 
 int dhaug_gemm_bf16_dmask(const uint16_t* A, int64_t lda, const uint16_t* B, int64_t ldb, const uint16_t* residual,
@@ -2698,17 +2192,7 @@ int dhaug_gemm_bf16_dbits_wide(const uint16_t* A, int64_t lda, const uint16_t* B
                 (bits_hi == nullptr || dhaug_aligned16(bits_hi)), DHAUG_EALIGN);
     GemmArgs p{A, lda, B, ldb, nullptr, nullptr, 0, nullptr, 0, c_bf16, ldc_bf16, N, nullptr, 0, M, N, K, N,
                DHAUG_ACT_NONE, 0.0f, nullptr, 0, dmask_act == DHAUG_ACT_RELU ? 0.0f : dmask_slope, bits_lo, bits_hi, 0};
-    hipStream_t s = (hipStream_t)stream;
-    switch (K / 16) {
-        case 1: return launch_ws<1>(s, p);
-        case 2: return launch_ws<2>(s, p);
-        case 3: return launch_ws<3>(s, p);
-        case 4: return launch_ws<4>(s, p);
-        case 7: return launch_ws<7>(s, p);
-        case 8: return launch_ws<8>(s, p);
-        case 16: return launch_ws<16>(s, p);
-        default: return DHAUG_EUNSUPPORTED;
-    }
+    return launch_ws_ksteps((int)(K / 16), (hipStream_t)stream, p);
 }
 
 /* see include/dhaug.h */
@@ -2735,12 +2219,7 @@ int dhaug_gemm_block2_stack_bf16(const uint16_t* X, int64_t ldx, const dhaug_blo
         a.b[i] = Block2One{b.W1, b.ldw1, b.W2, b.ldw2, b.bits1, b.bits2, b.Y1, b.ldy1, b.Y2, b.ldy2};
         in = b.Y2;
     }
-    static bool configured = false;
-    if (!configured) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_block2_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, B2_LDS);
-        if (e != hipSuccess) return (int)e;
-        configured = true;
-    }
+    if (const int rc = dhaug_dynamic_lds<gemm_block2_kernel>(B2_LDS)) return rc;
     const long long mtiles = M / B2_BM;
     hipLaunchKernelGGL(gemm_block2_kernel, dim3(dhaug_persistent_grid(mtiles)), dim3(512), B2_LDS, (hipStream_t)stream, a);
     return dhaug_launch_status();
@@ -2783,6 +2262,19 @@ int dhaug_gemm_tn_bf16_rows(const uint16_t* A, int64_t lda, const uint16_t* B, i
     DHAUG_CHECK(lda % 8 == 0 && ldb % 8 == 0 && lda >= ((N1 + 7) & ~7LL) && ldb >= ((N2 + 7) & ~7LL), DHAUG_EALIGN);
     DHAUG_CHECK(dhaug_aligned16(A) && dhaug_aligned16(B), DHAUG_EALIGN);
     const long long tiles = ((N1 + TN_BN - 1) / TN_BN) * ((N2 + TN_BN - 1) / TN_BN);
+    if (tn_route(M, N1, N2) == TN64) {
+        long long sp = 512 / tiles;                              // two resident workgroups per CU (LDS 64 KB each)
+        if (sp < 1) sp = 1;
+        long long r2 = ((M + sp - 1) / sp + TF_ROWS - 1) / TF_ROWS * TF_ROWS;
+        if (r2 < 2 * TF_ROWS) r2 = 2 * TF_ROWS;
+        sp = (M + r2 - 1) / r2;
+        if (sp > 8) sp = (sp + 7) / 8 * 8;
+        constexpr int lds = 2 * (TF_ROWS * 128 + TF_ROWS * 128);
+        if (const int rc = dhaug_dynamic_lds<gemm_tn64_kernel>(lds)) return rc;
+        TnArgs pf{A, lda, B, ldb, C, ldc, colsum_a, M, N1, N2, r2, tiles, sp, cs_rows};
+        hipLaunchKernelGGL(gemm_tn64_kernel, dim3((unsigned)(tiles * sp)), dim3(256), lds, s, pf);
+        return dhaug_launch_status();
+    }
     // about two resident workgroups per CU; few splits keep the atomic traffic (splits x N1 x N2 x 4 B) small
     long long splits = 768 / tiles;                              // three resident workgroups per CU (LDS 49 KB each)
     if (splits < 1) splits = 1;
@@ -2791,55 +2283,6 @@ int dhaug_gemm_tn_bf16_rows(const uint16_t* A, int64_t lda, const uint16_t* B, i
     if (rows < 4 * BK) rows = 4 * BK;
     splits = (M + rows - 1) / rows;
     if (splits > 8) splits = (splits + 7) / 8 * 8;              // multiple of 8: XCD-local tile groups (empty slices exit)
-    if (N1 % 128 == 0 && N2 % 128 == 0 && M % TB_ROWS == 0 && M >= 64 * 1024 && getenv("DHAUG_GEMM_GENERIC") == nullptr &&
-        getenv("DHAUG_TN_128") != nullptr) {          // measured SLOWER than the 64 x 64 tiles (12.5 vs 11.1 ms per GAN iteration): kept selectable
-        const long long tl = (N1 / 128) * (N2 / 128);
-        long long sp = 256 / tl;                                 // one workgroup per CU
-        if (sp < 1) sp = 1;
-        long long r2 = ((M + sp - 1) / sp + TB_ROWS - 1) / TB_ROWS * TB_ROWS;
-        if (r2 < 4 * TB_ROWS) r2 = 4 * TB_ROWS;
-        sp = (M + r2 - 1) / r2;
-        if (sp > 8) sp = (sp + 7) / 8 * 8;
-        static bool configured128 = false;
-        if (!configured128) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_tn128_kernel),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, TB_NSTG * TB_STG);
-            if (e != hipSuccess) return (int)e;
-            configured128 = true;
-        }
-        TnArgs pb{A, lda, B, ldb, C, ldc, colsum_a, M, N1, N2, r2, tl, sp, cs_rows};
-        hipLaunchKernelGGL(gemm_tn128_kernel, dim3((unsigned)(tl * sp)), dim3(256), TB_NSTG * TB_STG, s, pb);
-        return dhaug_launch_status();
-    }
-    static const bool tn_any = getenv("DHAUG_TN_NOPAD") == nullptr;     // (experiment switch: ragged N1 / N2 on the generic kernel)
-    const bool whole = N1 % TN_BN == 0 && N2 % TN_BN == 0;
-    if ((whole || (tn_any && M >= 16 * TF_ROWS)) && M % TF_ROWS == 0 && M >= 4 * TF_ROWS && getenv("DHAUG_GEMM_GENERIC") == nullptr) {
-        // 128 x 64 tiles (one workgroup per CU) re-read less from L2 but measured slower (35 vs 27 us at 65536 x 256 x 256):
-        // the loop is bound by requests in flight, not by L2 bandwidth.  Kept selectable for experiments.
-        const bool wide = whole && N1 % 128 == 0 && getenv("DHAUG_TN_WIDE") != nullptr;
-        const long long tl = wide ? tiles / 2 : tiles;
-        long long sp = (wide ? 256 : 512) / tl;
-        if (sp < 1) sp = 1;
-        long long r2 = ((M + sp - 1) / sp + TF_ROWS - 1) / TF_ROWS * TF_ROWS;
-        if (r2 < 2 * TF_ROWS) r2 = 2 * TF_ROWS;
-        sp = (M + r2 - 1) / r2;
-        if (sp > 8) sp = (sp + 7) / 8 * 8;
-        const int lds = wide ? 2 * (TF_ROWS * 256 + TF_ROWS * 128) : 2 * (TF_ROWS * 128 + TF_ROWS * 128);
-        static bool configured = false;
-        if (!configured) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_tn64_kernel<64>),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, 2 * (TF_ROWS * 128 + TF_ROWS * 128));
-            if (e == hipSuccess)
-                e = hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_tn64_kernel<128>),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, 2 * (TF_ROWS * 256 + TF_ROWS * 128));
-            if (e != hipSuccess) return (int)e;
-            configured = true;
-        }
-        TnArgs pf{A, lda, B, ldb, C, ldc, colsum_a, M, N1, N2, r2, tl, sp, cs_rows};
-        if (wide) hipLaunchKernelGGL(gemm_tn64_kernel<128>, dim3((unsigned)(tl * sp)), dim3(256), lds, s, pf);
-        else hipLaunchKernelGGL(gemm_tn64_kernel<64>, dim3((unsigned)(tl * sp)), dim3(256), lds, s, pf);
-        return dhaug_launch_status();
-    }
     TnArgs p{A, lda, B, ldb, C, ldc, colsum_a, M, N1, N2, rows, tiles, splits, cs_rows};
     hipLaunchKernelGGL(gemm_tn_kernel, dim3((unsigned)(tiles * splits)), dim3(256), 0, s, p);
     return dhaug_launch_status();

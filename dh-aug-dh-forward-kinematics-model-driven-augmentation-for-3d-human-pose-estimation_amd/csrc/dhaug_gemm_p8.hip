@@ -487,11 +487,6 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_p8_group_kernel(GemmGroupArgs 
     }
 }
 
-template <typename Kern>
-int p8_configure(Kern kern) {
-    return (int)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, P_LDS);
-}
-
 }  // namespace
 
 bool dhaug_p8_supported(const dhaug_gemm::GemmArgs& p) {
@@ -525,12 +520,7 @@ extern "C" int dhaug_debug_p8_stamps(long long* out, int n) {
 
 template <bool F16>
 static int p8_launch_single(hipStream_t s, const dhaug_gemm::GemmArgs& p) {
-    static bool configured = false;
-    if (!configured) {
-        const int e = p8_configure(gemm_nt_p8_kernel<F16>);
-        if (e != 0) return e;
-        configured = true;
-    }
+    if (const int rc = dhaug_dynamic_lds<gemm_nt_p8_kernel<F16>>(P_LDS)) return rc;
     const long long grid = (((p.M + P_BM - 1) / P_BM + 7) / 8 * 8) * ((p.W + P_BN - 1) / P_BN);
     DHAUG_CHECK(grid <= 0x7fffffffLL, DHAUG_EUNSUPPORTED);
     hipLaunchKernelGGL(gemm_nt_p8_kernel<F16>, dim3((unsigned)grid), dim3(512), P_LDS, s, p);
@@ -540,12 +530,7 @@ int dhaug_p8_launch(hipStream_t s, const dhaug_gemm::GemmArgs& p) { return p8_la
 int dhaug_p8_launch_f16(hipStream_t s, const dhaug_gemm::GemmArgs& p) { return p8_launch_single<true>(s, p); }
 
 int dhaug_p8_launch_group(hipStream_t s, const dhaug_gemm::GemmGroupArgs& g, int n) {
-    static bool configured = false;
-    if (!configured) {
-        const int e = p8_configure(gemm_nt_p8_group_kernel);
-        if (e != 0) return e;
-        configured = true;
-    }
+    if (const int rc = dhaug_dynamic_lds<gemm_nt_p8_group_kernel>(P_LDS)) return rc;
     const dhaug_gemm::GemmArgs& p = g.g[0];
     const long long tiles = ((p.M + P_BM - 1) / P_BM) * ((p.W + P_BN - 1) / P_BN);
     long long grid = tiles * n;

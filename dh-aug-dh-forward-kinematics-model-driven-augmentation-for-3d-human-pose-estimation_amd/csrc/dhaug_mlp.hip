@@ -1393,13 +1393,7 @@ __global__ __launch_bounds__(MLP_THREADS, 1) void fused_mlp_kernel(Program prog,
 // carried the save pointers the instantiation spilled, and hipcc 7.2's "AMDGPU Rewrite AGPR-Copy-MFMA" pass crashes on
 // spilled MFMA code under -amdgpu-mfma-vgpr-form; reading them from the kernarg segment at the save removed both.)
 extern "C" __attribute__((visibility("hidden"))) int dhaug_mlp_launch_save_(const void* prog, long long M, unsigned grid, void* stream) {
-    static bool configured = false;
-    if (!configured) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(fused_mlp_kernel<true>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, MLP_LDS_BYTES);
-        if (e != hipSuccess) return (int)e;
-        configured = true;
-    }
+    if (const int rc = dhaug_dynamic_lds<fused_mlp_kernel<true>>(MLP_LDS_BYTES)) return rc;
     hipLaunchKernelGGL(fused_mlp_kernel<true>, dim3(grid), dim3(MLP_THREADS), MLP_LDS_BYTES, (hipStream_t)stream,
                        *static_cast<const Program*>(prog), M);
     return dhaug_launch_status();
@@ -1604,18 +1598,12 @@ int dhaug_mlp_forward(const dhaug_mlp_unit* units, int nunits, int64_t M, void* 
         }
         for (int i = 0; i < prog.nunits; ++i) DHAUG_CHECK(prog.u[i].bits == nullptr || in_run[i], DHAUG_EUNSUPPORTED);
     }
-    static bool configured = false;
-    if (!configured) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(fused_mlp_kernel<false>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, MLP_LDS_BYTES);
-        if (e != hipSuccess) return (int)e;
-        configured = true;
-    }
     const long long ntiles = (M + MLP_BM - 1) / MLP_BM;
     const unsigned grid = dhaug_persistent_grid(ntiles);           // one persistent workgroup per CU
     // forward-with-save (a unit asks for its image in global memory) is a second instantiation: the inference kernel's
     // schedule is exactly what it was
     if (any_save) return dhaug_mlp_launch_save_(&prog, (long long)M, grid, stream);        // (csrc/dhaug_mlp_save.hip)
+    if (const int rc = dhaug_dynamic_lds<fused_mlp_kernel<false>>(MLP_LDS_BYTES)) return rc;
     hipLaunchKernelGGL(fused_mlp_kernel<false>, dim3(grid), dim3(MLP_THREADS), MLP_LDS_BYTES, (hipStream_t)stream, prog, (long long)M);
     return dhaug_launch_status();
 }

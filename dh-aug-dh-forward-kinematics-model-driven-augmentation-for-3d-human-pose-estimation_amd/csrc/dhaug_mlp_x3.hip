@@ -1319,25 +1319,17 @@ int dhaug_mlp_forward_x3(const dhaug_mlp_unit* units, int nunits, int64_t M, voi
 #if !X3_SHAPE16
     DHAUG_CHECK(t16 != 1, DHAUG_EUNSUPPORTED);
 #endif
-    static bool configured = false;
-    if (!configured) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(fused_mlp_x3_kernel<false>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, X3_LDS_BYTES);
-        if (e != hipSuccess) return (int)e;
-#if X3_SHAPE16
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(fused_mlp_x3_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                X3_LDS_BYTES);
-        if (e != hipSuccess) return (int)e;
-#endif
-        configured = true;
-    }
     const long long ntiles = (M + X3_BM - 1) / X3_BM;
     const unsigned grid = dhaug_persistent_grid(ntiles);           // one persistent workgroup per CU
 #if X3_SHAPE16
-    if (t16 == 1) hipLaunchKernelGGL(fused_mlp_x3_kernel<true>, dim3(grid), dim3(X3_THREADS), X3_LDS_BYTES, (hipStream_t)stream, prog, (long long)M);
-    else
+    if (t16 == 1) {
+        if (const int rc = dhaug_dynamic_lds<fused_mlp_x3_kernel<true>>(X3_LDS_BYTES)) return rc;
+        hipLaunchKernelGGL(fused_mlp_x3_kernel<true>, dim3(grid), dim3(X3_THREADS), X3_LDS_BYTES, (hipStream_t)stream, prog, (long long)M);
+        return dhaug_launch_status();
+    }
 #endif
-        hipLaunchKernelGGL(fused_mlp_x3_kernel<false>, dim3(grid), dim3(X3_THREADS), X3_LDS_BYTES, (hipStream_t)stream, prog, (long long)M);
+    if (const int rc = dhaug_dynamic_lds<fused_mlp_x3_kernel<false>>(X3_LDS_BYTES)) return rc;
+    hipLaunchKernelGGL(fused_mlp_x3_kernel<false>, dim3(grid), dim3(X3_THREADS), X3_LDS_BYTES, (hipStream_t)stream, prog, (long long)M);
     return dhaug_launch_status();
 }
 

@@ -432,16 +432,10 @@ int dhaug_gemm_tn_group_bf16_phase(const dhaug_tn_layer* layers, int n, float* w
     static const bool xcd_deal = getenv("DHAUG_TN_NO_XCD_DEAL") == nullptr;
     if (wide && xcd_deal) { g.abl |= 16; wg = (wg + 7) & ~7; }     // (workgroups beyond the last layer's range return at once)
     hipStream_t s = (hipStream_t)stream;
-    static bool configured = false;
-    if (!configured) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_tn_group_kernel),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, T2_LDS);
-        if (e != hipSuccess) return (int)e;
-        configured = true;
-    }
     // phase 1: the partial results only; phase 2: only their sums into the gradient slots (the same dealing, recomputed from
     // the same descriptors); 0: both
     if (phase != 2) {
+        if (const int e = dhaug_dynamic_lds<gemm_tn_group_kernel>(T2_LDS)) return e;
         hipLaunchKernelGGL(gemm_tn_group_kernel, dim3((unsigned)wg), dim3(512), T2_LDS, s, g);
         int rc = dhaug_launch_status();
         if (rc != DHAUG_OK || phase == 1) return rc;

@@ -559,12 +559,7 @@ int dhaug_critic_top_backward_bf16(const dhaug_top_desc* d, void* stream) {
     DHAUG_CHECK(dhaug_aligned16(d->m1) && dhaug_aligned16(d->mh) && dhaug_aligned16(d->m0) && dhaug_aligned16(d->w2) && dhaug_aligned16(d->w1) &&
                 dhaug_aligned16(d->wm) && dhaug_aligned16(d->g2) && dhaug_aligned16(d->g1) && dhaug_aligned16(d->g0) && dhaug_aligned16(d->gcat) &&
                 dhaug_aligned16(d->bits0) && dhaug_aligned16(d->bits1), DHAUG_EALIGN);
-    static bool configured = false;
-    if (!configured) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(top_backward_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, T_LDS);
-        if (e != hipSuccess) return (int)e;
-        configured = true;
-    }
+    if (const int rc = dhaug_dynamic_lds<top_backward_kernel>(T_LDS)) return rc;
     TopArgs a{};
     a.seed = d->seed; a.ld_seed = d->ld_seed; a.wout = d->wout; a.ld_wout = d->ld_wout;
     a.m1 = const_cast<uint16_t*>(d->m1); a.mh = const_cast<uint16_t*>(d->mh); a.m0 = const_cast<uint16_t*>(d->m0); a.ld_m = d->ld_m;
@@ -590,12 +585,7 @@ int dhaug_critic_top_tangent_bf16(const dhaug_top_desc* d, void* stream) {
     DHAUG_CHECK(d->ld_m % 8 == 0 && d->ldw2 % 8 == 0 && d->ldw1 % 8 == 0 && d->ldwm % 8 == 0 && d->ldx % 8 == 0, DHAUG_EALIGN);
     DHAUG_CHECK(dhaug_aligned16(d->m1) && dhaug_aligned16(d->mh) && dhaug_aligned16(d->m0) && dhaug_aligned16(d->w2) && dhaug_aligned16(d->w1) &&
                 dhaug_aligned16(d->wm) && dhaug_aligned16(d->x), DHAUG_EALIGN);
-    static bool configured = false;
-    if (!configured) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(top_tangent_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, T_LDS);
-        if (e != hipSuccess) return (int)e;
-        configured = true;
-    }
+    if (const int rc = dhaug_dynamic_lds<top_tangent_kernel>(T_LDS)) return rc;
     TopArgs a{};
     a.x = d->x; a.ldx = d->ldx;
     a.m1 = const_cast<uint16_t*>(d->m1); a.mh = const_cast<uint16_t*>(d->mh); a.m0 = const_cast<uint16_t*>(d->m0); a.ld_m = d->ld_m;

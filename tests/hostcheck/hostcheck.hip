@@ -1,6 +1,8 @@
 // TEST-ONLY: runs the per-pose FK arithmetic of csrc/dhaug_fk_math.h on the HOST so that the container
-// without a GPU can compare it with the oracle (tests/test_hostcheck_cpu.py).  Never loaded by the product.
+// without a GPU can compare it with the oracle (tests/test_hostcheck_cpu.py), and exports the GEMM dispatchers' routing
+// functions (csrc/dhaug_gemm_route.h).  Never loaded by the product.
 #include "dhaug_fk_math.h"
+#include "dhaug_gemm_route.h"
 using namespace dhaug_fk;
 
 extern "C" void hostcheck_fk_forward(const float* ang, const float* bl, const float* root, float* out16, long N) {
@@ -39,3 +41,14 @@ extern "C" void hostcheck_tail_angles(const float* head, float* ang, float* root
 extern "C" void hostcheck_sincos(const float* x, float* s, float* c, long N) {
     for (long n = 0; n < N; ++n) sincos_rad(x[n], s[n], c[n]);
 }
+
+// the NT dispatcher's choice: 100 * dhaug_route::NtKernel + ksteps.  wide_min_tiles < 0: the default
+extern "C" int hostcheck_nt_route(long long M, long long N, long long W, long long K, int out_bf16, int out_f32, int res_f32, int bias_ok,
+                                  int mask_f32, int p8_ok, int no256, int nobig, int nop8, long long wide_min_tiles) {
+    const dhaug_route::NtShape s{M, N, W, K, out_bf16 != 0, out_f32 != 0, res_f32 != 0, bias_ok != 0, mask_f32 != 0, p8_ok != 0,
+                                 no256 != 0, nobig != 0, nop8 != 0, wide_min_tiles < 0 ? dhaug_route::WIDE_MIN_TILES_DEFAULT : wide_min_tiles};
+    const dhaug_route::NtRoute r = dhaug_route::nt_route(s);
+    return 100 * (int)r.kernel + r.ksteps;
+}
+
+extern "C" int hostcheck_tn_route(long long M, long long N1, long long N2) { return (int)dhaug_route::tn_route(M, N1, N2); }

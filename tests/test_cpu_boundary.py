@@ -308,6 +308,75 @@ def test_hostcheck_fk_math_matches_oracle(built):
         assert np.abs(got - ref.numpy()).max() <= 1e-4 * ref.abs().max().item()
 
 
+# (M, N, K, what differs from the defaults, kernel, KSTEPS / KS).  Defaults: bf16 output only, no fp32 residual, no fp32 mask, bias
+# aligned, W = N, p8_ok, no switch set.  Derived by hand from the dispatcher as it was before the routing became a function of its own.
+NT_ROUTES = [
+    (4096, 256, 256, {}, "NT256S", 16),
+    (4096, 256, 128, {}, "NT256S", 8),
+    (4128, 256, 256, {}, "WS", 16),                                  # M % 64 != 0
+    (4096, 256, 256, {"out_f32": 1}, "WS", 16),
+    (4096, 256, 256, {"res_f32": 1}, "WS", 16),
+    (4096, 256, 256, {"bias_ok": 0}, "WS", 16),
+    (4096, 256, 256, {"no256": 1}, "WS", 16),
+    (4096, 256, 64, {}, "WS", 4),
+    (4096, 256, 112, {}, "WS", 7),
+    (4096, 256, 80, {}, "PIPE2", 0),
+    (4096, 256, 96, {}, "PIPE2", 0),
+    (4096, 256, 272, {}, "PIPE2", 0),
+    (4096, 65, 16, {}, "WS", 1),
+    (4096, 60, 256, {"W": 128}, "WS", 16),                           # zero-padded output
+    (4096, 64, 256, {}, "GENERIC_128x64", 0),
+    (4096, 33, 256, {}, "GENERIC_128x64", 0),
+    (4096, 32, 256, {}, "GENERIC_128x32", 0),
+    (4096, 512, 256, {}, "WS", 16),                                  # ws precedes big
+    (4096, 512, 272, {}, "BIG", 0),
+    (4096, 1000, 1008, {}, "BIG", 0),
+    (4095, 1000, 1008, {}, "PIPE2", 0),
+    (13824, 1000, 1008, {}, "P8", 0),
+    (13824, 1000, 1008, {"nop8": 1}, "WIDE", 0),
+    (13824, 1000, 1008, {"p8_ok": 0}, "WIDE", 0),
+    (13824, 1000, 1008, {"nobig": 1}, "PIPE2", 0),
+    (40960, 256, 768, {}, "P8", 0),                                  # 160 tiles
+    (40704, 256, 768, {}, "PIPE2", 0),                               # 159 tiles, W < 512
+    (40705, 256, 768, {}, "P8", 0),                                  # the ceiling gives 160
+    (512, 256, 768, {"wide_min_tiles": 1}, "P8", 0),
+    (4096, 256, 256, {"mask_f32": 1, "out_bf16": 0, "out_f32": 1}, "PIPE2", 0),
+    (4096, 256, 48, {"mask_f32": 1, "out_bf16": 0, "out_f32": 1}, "GENERIC_128x128", 0),
+    (4096, 64, 48, {"mask_f32": 1, "out_bf16": 0, "out_f32": 1}, "GENERIC_128x64", 0),
+]
+TN_ROUTES = [
+    (4096, 256, 256, "TN64"), (512, 64, 64, "TN64"), (384, 64, 64, "TN_GENERIC"), (1920, 64, 128, "TN64"),
+    (1920, 100, 100, "TN_GENERIC"), (6144, 100, 100, "TN64"), (12288, 1, 100, "TN64"), (1000, 100, 512, "TN_GENERIC"),
+    (65728, 128, 384, "TN_GENERIC"),
+]
+
+
+def test_gemm_routes(built):
+    """which kernel the NT and TN dispatchers of csrc/dhaug_gemm.hip take for a shape: csrc/dhaug_gemm_route.h, the very functions
+    the dispatchers call, compiled for the host."""
+    lib = ctypes.CDLL(os.path.join(ROOT, "tests", "hostcheck", "_build", "libhostcheck.so"))
+    LL = ctypes.c_longlong
+    lib.hostcheck_nt_route.argtypes = [LL] * 4 + [ctypes.c_int] * 9 + [LL]
+    lib.hostcheck_tn_route.argtypes = [LL] * 3
+    nt_names = ["NT256S", "WS", "P8", "WIDE", "BIG", "PIPE2", "GENERIC_128x128", "GENERIC_128x64", "GENERIC_128x32"]   # enum NtKernel
+    tn_names = ["TN64", "TN_GENERIC"]                                                                                   # enum TnKernel
+    bad = []
+    for M, N, K, extra, kernel, ks in NT_ROUTES:
+        a = dict(W=N, out_bf16=1, out_f32=0, res_f32=0, bias_ok=1, mask_f32=0, p8_ok=1, no256=0, nobig=0, nop8=0, wide_min_tiles=-1)
+        assert set(extra) <= set(a)
+        a.update(extra)
+        r = lib.hostcheck_nt_route(M, N, a["W"], K, a["out_bf16"], a["out_f32"], a["res_f32"], a["bias_ok"], a["mask_f32"], a["p8_ok"],
+                                   a["no256"], a["nobig"], a["nop8"], a["wide_min_tiles"])
+        got = (nt_names[r // 100], r % 100)
+        if got != (kernel, ks):
+            bad.append(((M, N, K, extra), got, (kernel, ks)))
+    for M, N1, N2, kernel in TN_ROUTES:
+        got = tn_names[lib.hostcheck_tn_route(M, N1, N2)]
+        if got != kernel:
+            bad.append(((M, N1, N2), got, kernel))
+    assert not bad, bad
+
+
 def test_hostcheck_under_address_and_ub_sanitizers(built, tmp_path):
     """the same host build as an executable under -fsanitize=address,undefined (-fno-sanitize-recover): ordinary poses and
     the degenerate ones of tests/test_gpu_edge.py (angles of +-1e4 and +-1e7 degrees -- the library path of the range

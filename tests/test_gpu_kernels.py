@@ -190,7 +190,9 @@ def _bf(t):
 
 @pytest.mark.parametrize("M,N,K", [(256, 256, 256), (1000, 256, 128), (129, 100, 512), (4096, 35, 256), (777, 1, 112),
                                    (64, 256, 48), (300, 256, 32), (2048, 112, 112), (515, 315, 1008),
-                                   # long batch x wide layer: the 128 x 256-tile kernel (ragged rows, K tail, ragged columns)
+                                   # long batch x wide layer (ragged rows, K tail, ragged columns): the 128 x 256-tile kernel; K = 256,
+                                   # which the weight-stationary kernel takes before the big tiles are asked; the 256 x 256-tile
+                                   # ping-pong kernel (216 tiles)
                                    (4608, 1000, 1008), (4096 + 77, 512, 256), (13824, 1000, 1008)])
 def test_gemm_nt_plain(ops, M, N, K):
     gen = torch.Generator().manual_seed(M + N + K)
@@ -199,6 +201,28 @@ def test_gemm_nt_plain(ops, M, N, K):
     ref = (A.float().cpu().double() @ B.float().cpu().double().t()).float()
     _, cf = ops.gemm_nt(A, B, N, K, out_f32=True)
     assert maxabs(cf, ref) <= 2e-5 * max(1.0, ref.abs().max().item())
+
+
+def test_gemm_nt_on_a_second_device(ops, monkeypatch):
+    """kernels that need more than 64 KB of dynamic LDS get the attribute per DEVICE (dhaug_dynamic_lds, csrc/dhaug_common.h): the
+    ping-pong kernel (139 264 bytes; reached at 512 rows through DHAUG_GEMM_WIDE_MIN_TILES=1) and the two-role 256-wide kernel, first on
+    device 0 and then, in the same process, on device 1.  The fp32 result holds test_gemm_nt_plain's bound against the fp64 product;
+    the 256-wide kernel returns bf16, so its bound has one bf16 rounding of the largest result (2^-8 of it) on top."""
+    if torch.cuda.device_count() < 2:
+        pytest.skip("needs two devices")
+    monkeypatch.setenv("DHAUG_GEMM_WIDE_MIN_TILES", "1")
+    for dev in (0, 1):
+        with torch.cuda.device(dev):
+            for M, N, K, f32 in ((512, 256, 768, True), (128, 256, 256, False)):
+                gen = torch.Generator().manual_seed(M + N + K)
+                A = _bf(torch.randn(M, K, generator=gen)).cuda()
+                B = _bf(torch.randn(N, K, generator=gen) / K ** 0.5).cuda()
+                ref = (A.float().cpu().double() @ B.float().cpu().double().t()).float()
+                scale = max(1.0, ref.abs().max().item())
+                cb, cf = ops.gemm_nt(A, B, N, K, out_f32=f32, out_bf16=not f32)
+                got = cf if f32 else cb.float()
+                assert got.device.index == dev
+                assert maxabs(got, ref) <= (2e-5 if f32 else 2e-5 + 2.0 ** -8) * scale, (dev, M, N, K)
 
 
 @pytest.mark.parametrize("act,slope", [(0, 0.0), (1, 0.0), (2, 0.01)])
@@ -381,9 +405,10 @@ def test_gemm_nt_group_128_tiles_equal_single_launches(ops, M, n):
                                                             (192, 128, 0, 0.0, False, True), (64, 256, 1, 0.0, False, False),
                                                             (33280, 128, 1, 0.0, True, True)])
 def test_gemm_nt_256wide(ops, M, K, act, slope, use_bias, use_res):
-    """The weight-stationary 256-feature kernel of the training path (rows copied global->LDS, residual on the matrix
+    """The two-role 256-feature kernel of the training path (gemm_nt256s_kernel: rows copied global->LDS, residual on the matrix
     pipe): bf16 output bit-identical to rounding the fp64 reference except where fp32 accumulation order moves a value
-    across a rounding boundary (<= 1 bf16 ulp), and identical to the generic kernel's within the same bound."""
+    across a rounding boundary (<= 1 bf16 ulp), and identical within the same bound to that of the weight-stationary kernel
+    (gemm_nt_ws_kernel), which takes these shapes under DHAUG_GEMM_NO256."""
     import os
     N = 256
     gen = torch.Generator().manual_seed(M + K + act)
@@ -427,7 +452,7 @@ def test_gemm_split_terms(ops, terms, tol):
 
 
 @pytest.mark.parametrize("M,N1,N2", [(4096, 256, 256), (1000, 100, 512), (777, 32, 256), (65536, 256, 48), (130, 1, 100),
-                                     (98304, 256, 256), (65536 + 192, 128, 384),  # (these two also run under DHAUG_TN_128=1 by hand)
+                                     (98304, 256, 256), (65536 + 192, 128, 384),  # (long contractions; 65 728 rows are not whole 128-row stages: the register-staged kernel)
                                      # ragged feature counts on whole 128-row stages: the LDS-DMA kernel with zero-sourced chunks
                                      (6144, 100, 100), (12288, 1, 100), (12288, 256, 30), (98304, 100, 512), (6144, 1, 256)])
 def test_gemm_tn(ops, M, N1, N2):
@@ -558,7 +583,7 @@ def test_split_of_a_column_view_reads_it_in_place(ops):
 def test_gemm_split_operand_mask_in_the_epilogue(ops):
     """dhaug_gemm_bf16_dmask_f32: (A B^T + res) * relu'(mask) with fp32 result / residual / mask on six-term split operands -- the
     backward / tangent GEMM of the parity-grade training step -- against fp64 and against the GEMM + dhaug_act_backward_f32 pair it
-    replaces (long batch: the 256 x 256-tile kernel; short: the 64 x 64 one; a ragged width)"""
+    replaces (long batch, 161 tiles: the 256 x 256-tile kernel; short: the 64 x 64 one; a ragged width on the 128 x 256-tile kernel)"""
     gen = torch.Generator().manual_seed(31)
     for M, N, K in ((40960 + 24, 256, 256), (300, 100, 256), (4096, 1000, 48)):
         a = torch.randn(M, K, generator=gen)
@@ -913,7 +938,8 @@ def test_gemm_block2_stack_equals_single_blocks(ops, M, nb):
 @pytest.mark.parametrize("M,N,K,act,slope,use_res", [(4096, 256, 256, 1, 0.0, False), (4096, 256, 256, 2, 0.01, False),
                                                    (1024, 256, 128, 1, 0.0, True), (1000, 104, 256, 1, 0.0, False)])
 def test_gemm_nt_dmask(ops, M, N, K, act, slope, use_res):
-    """(A B^T + res) * act'(y): mask in the 256-wide kernel's epilogue, GEMM + dhaug_act_backward_bf16 elsewhere"""
+    """(A B^T + res) * act'(y): the mask from an LDS image of its own in the two-role 256-wide kernel (K = 128, 256), in the coalesced
+    epilogue of every other kernel (here the weight-stationary one: N = 104)"""
     gen = torch.Generator().manual_seed(M + N + act)
     A = _bf(torch.randn(M, K, generator=gen)).cuda()
     B = _bf(torch.randn(N, K, generator=gen) / K ** 0.5).cuda()
