@@ -32,13 +32,9 @@ from . import ops
 # sweep 1 (forward) of the single-frame critics as ONE fused launch that also saves every layer's output
 # (fused.critic3d_forward_save / critic2d_forward_save) instead of one GEMM launch per layer; bf16 arithmetic only
 FUSED_STEP_FORWARD = os.environ.get("DHAUG_NO_FUSED_STEP_FORWARD") is None
-# sweep 4: the weight / bias gradients of all layers up to 256 wide in ONE grouped launch (ops.gemm_tn_group) instead of one
-# contraction launch per layer
-TN_GROUP = os.environ.get("DHAUG_NO_TN_GROUP") is None
 # the forward-with-save launch writes the block layers' images for the real / fake rows only (the interpolated rows are read
 # through their sign bits alone, and receive the tangents): a third fewer stores in the launch that pays most for them
 SKIP_XHAT_SAVES = os.environ.get("DHAUG_SAVE_ALL_ROWS") is None
-RANK1 = os.environ.get("DHAUG_NO_RANK1") is None
 # sweep 4 in two parts: the real / fake rows' contractions are launched on a side stream right behind the backward chain and
 # run (HBM-bound) beside the penalty and the launch-bound tangent sweep; the interpolated rows' part follows the tangents
 TN_SPLIT = os.environ.get("DHAUG_NO_TN_SPLIT") is None
@@ -50,10 +46,6 @@ _TN_SIDE = {}
 # 96 -> 7.10 ms, 112 -> 6.91, 128 -> 6.64, 144 -> 6.67, 160 -> 6.60; another: 128 -> 6.49 (three runs), 160 -> 6.46, 192 -> 6.46,
 # 224 -> 6.39, 256 -> 6.40 (four runs, 6.35 - 6.44); the video iteration does not care (13.25 either way)
 TN_SIDE_WGS = int(os.environ.get("DHAUG_TN_SIDE_WGS", "256"))
-# the second part's contractions started beside what is left of the first (only the sums wait): measured 6.87 against 6.94 ms
-# per iteration -- the contractions are HBM-bound either way -- so it is an option, off
-TN_PHASED = os.environ.get("DHAUG_TN_PHASED") is not None
-TN_MAIN_WGS = int(os.environ.get("DHAUG_TN_MAIN_WGS", "0"))  # workgroups of the second part (0: one per CU)
 
 # the layers of independent branches at the same depth as ONE launch (_Math.mm_group, dhaug_gemm_bf16_group): a motion critic's four /
 # two branch layers.  On by default since round 5 (DHAUG_NO_NT_GROUP=1: one launch per layer): the grouped launch runs on 128 x 128
@@ -61,8 +53,6 @@ TN_MAIN_WGS = int(os.environ.get("DHAUG_TN_MAIN_WGS", "0"))  # workgroups of the
 # (Round 4's form, the same launch on 64 x 64 tiles = 1 536 workgroups: 35 us alone against 4 x 12.7, but 17.2 ms per video iteration
 # against 15.4 -- it left no slots to the other three critics' streams; DHAUG_NT_GROUP_TILE=64 still selects it.)
 NT_GROUP = os.environ.get("DHAUG_NO_NT_GROUP") is None
-# split-operand arithmetic: one activation-side split per tensor and step (_Math.split0); DHAUG_NO_SPLIT_CACHE=1: one per use
-SPLIT_CACHE = os.environ.get("DHAUG_NO_SPLIT_CACHE") is None
 # split-operand arithmetic ("bf16x6"): an operand whose padded width is 64 * 2^j is split into its three distinct pieces ONCE, as planes
 # [hi | mid | lo] (6 bytes per value instead of 12, and one split where the forward / backward chains and sweep 4 wanted two layouts);
 # the layer products (ops.gemm_nt_planes) and the grouped weight-gradient launch read the pieces in the order of the six-segment operand --
@@ -112,6 +102,7 @@ class _Math:
         self.tn2, self._tn_slots = [], set()         # split-operand arithmetic: second contributions to a slot already in self.tn
         self._splits, self._split_src = [], []       # split-operand arithmetic: (address, rows, cols, mode, split) of this step
         self._casts = {}                             # bf16: the casts of fp32 inputs made in this step
+        self._side = None                            # (stream, items) of sweep 4's part under way on a side stream (flush_side)
 
     def width(self, n):
         return ceil16(n) if self.bf16 else n
@@ -165,7 +156,7 @@ class _Math:
             return hit
         p, rows, cols = a.data_ptr(), a.shape[0], a.shape[1]
         sp = ops.split_bf16(a, mode, self.T, ceil16(k))
-        if SPLIT_CACHE and cols == k:
+        if cols == k:
             self._splits.append((p, rows, cols, mode, sp))
             self._split_src.append(a)                # (referenced until flush: no address is reused inside a step)
         return sp
@@ -177,7 +168,7 @@ class _Math:
 
     def cached_split(self, a, k, mode):
         """the split of (a row range of) this tensor made earlier in the step, or None"""
-        if not (SPLIT_CACHE and a.is_contiguous() and a.shape[1] == k):
+        if not (a.is_contiguous() and a.shape[1] == k):
             return None
         p, rows, cols = a.data_ptr(), a.shape[0], a.shape[1]
         for bp, brows, bcols, bmode, sp in self._splits:
@@ -187,53 +178,48 @@ class _Math:
                     return sp if (r0 == 0 and rows == brows) else sp[r0:r0 + rows]
         return None
 
+    def _planes_epilogue(self, n, kp, bias, res, mask, mask_act, out, six):
+        """(res, mask) as ops.gemm_nt_planes takes them -- fp32 rows; the mask only where it acts -- or None where it cannot take this product"""
+        dm = mask if (mask is not None and mask_act != NONE) else None
+        resc = res if (res is None or res.is_contiguous()) else res.contiguous()
+        f32rows = lambda t: t is None or (t.dtype == torch.float32 and t.stride(1) == 1)
+        if (resc is None or resc.dtype == torch.float32) and f32rows(dm) and f32rows(out) and ops.gemm_planes_ok(n, kp, bias, resc, dm, out, six=six):
+            return resc, dm
+        return None
+
+    def _register_planes(self, y, n, yp):
+        """yp, the planes a GEMM wrote beside its result y, are this step's split of y: no split launch for it"""
+        self._splits.append((y.data_ptr(), y.shape[0], n, 2, yp))
+        self._split_src.append(y)
+        return y
+
     def mm(self, a, W, orient, bias=None, res=None, act=NONE, slope=0.0, mask=None, mask_act=NONE, out=None, out_f32=False):
         """(a @ W^T if orient == 'nt' else a @ W) + bias + res, then act(.) or, with `mask`, * mask_act'(mask)."""
         N, K = W.shape
         n, k = (N, K) if orient == "nt" else (K, N)
         kp = ceil16(k)
-        if (self.planes_ok(k) and a.dtype == torch.float32 and a.dim() == 2 and a.stride(1) == 1
-                and self.cached_split(a, k, 1 if (orient == "nn" and SPLIT_CACHE) else 0) is None):   # (a six-segment split made for a product the ping-pong kernel does not take serves this one too)
-            masked = mask is not None and mask_act != NONE
-            resc = res if (res is None or res.is_contiguous()) else res.contiguous()
-            if ((resc is None or resc.dtype == torch.float32) and (not masked or (mask.dtype == torch.float32 and mask.stride(1) == 1))
-                    and (out is None or (out.dtype == torch.float32 and out.stride(1) == 1))
-                    and ops.gemm_planes_ok(n, kp, bias, resc, mask if masked else None, out)):
-                swap = orient == "nn" and SPLIT_CACHE        # (the weights' operand copies as below)
-                Bop = A._w_nt(W, kp, self.prec) if orient == "nt" else A._w_nn(W, self.prec, 0 if swap else 1)
-                # a result that is itself an operand of that width (the next layer's input, sweep 4's) leaves the GEMM with its planes
-                # beside it -- registered as this step's split of the tensor: no split launch for it
-                emit = PLANES_OUT and SPLIT_CACHE and self.planes_ok(n) and ceil16(n) == n and (out is None or out.is_contiguous())
-                r = ops.gemm_nt_planes(self.split0(a, k, 2), Bop, n, kp, bias=bias, res_f32=resc, act=act, slope=slope,
-                                       dmask_f32=mask if masked else None, dmask_act=mask_act if masked else NONE, dmask_slope=slope,
-                                       out=out, x_order=1 if swap else 0, planes_out=emit)
-                if emit:
-                    y, yp = r
-                    self._splits.append((y.data_ptr(), y.shape[0], n, 2, yp))
-                    self._split_src.append(y)
-                    return y
-                return r
-        if (PLANES_OUT and SPLIT_CACHE and orient == "nt" and not self.bf16 and self.T == 6 and not self.planes_ok(k) and self.planes_ok(n)
-                and ceil16(n) == n and a.dtype == torch.float32 and a.dim() == 2 and a.stride(1) == 1 and (out is None or out.is_contiguous())):
-            # a narrow input layer (30 / 48 -> DenseDim) whose result is an operand of plane width: the six-segment product on the same
-            # kernel, which writes the result's planes beside it
-            masked = mask is not None and mask_act != NONE
-            resc = res if (res is None or res.is_contiguous()) else res.contiguous()
-            if ((resc is None or resc.dtype == torch.float32) and (not masked or (mask.dtype == torch.float32 and mask.stride(1) == 1))
-                    and (out is None or (out.dtype == torch.float32 and out.stride(1) == 1))
-                    and ops.gemm_planes_ok(n, kp, bias, resc, mask if masked else None, out, six=True)):
-                y, yp = ops.gemm_nt_planes(self.split0(a, k, 0), A._w_nt(W, kp, self.prec), n, kp, bias=bias, res_f32=resc, act=act, slope=slope,
-                                           dmask_f32=mask if masked else None, dmask_act=mask_act if masked else NONE, dmask_slope=slope,
-                                           out=out, x_order=2, planes_out=True)
-                self._splits.append((y.data_ptr(), y.shape[0], n, 2, yp))
-                self._split_src.append(y)
-                return y
         # split-operand arithmetic, backward chain (orient "nn"): the cotangent is split ONCE, in the weight-side layout -- the
         # layout sweep 4 contracts it in (autograd_ops._raw_outer) -- and meets the weights in the activation-side layout
-        swap = (not self.bf16) and orient == "nn" and SPLIT_CACHE
+        swap = (not self.bf16) and orient == "nn"
+        f32rows = (not self.bf16) and a.dtype == torch.float32 and a.dim() == 2 and a.stride(1) == 1
+        # a result that is itself an operand of plane width (the next layer's input, sweep 4's) leaves the GEMM with its planes beside it
+        emit = PLANES_OUT and self.planes_ok(n) and ceil16(n) == n and (out is None or out.is_contiguous())
+        plan = None                                  # (x_order, mode of the activation-side split, six-segment operand, emit)
+        if self.planes_ok(k) and f32rows and self.cached_split(a, k, 1 if swap else 0) is None:   # (a six-segment split made for a product the ping-pong kernel does not take serves this one too)
+            plan = (1 if swap else 0, 2, False, emit)
+        elif emit and orient == "nt" and not self.planes_ok(k) and f32rows:
+            # a narrow input layer (30 / 48 -> DenseDim) whose result is an operand of plane width: the six-segment product on the same
+            # kernel, which writes the result's planes beside it
+            plan = (2, 0, True, True)
         Bop = A._w_nt(W, kp, self.prec) if orient == "nt" else A._w_nn(W, self.prec, 0 if swap else 1)
+        ep = None if plan is None else self._planes_epilogue(n, kp, bias, res, mask, mask_act, out, plan[2])
+        if ep is not None:
+            (x_order, mode, _, emit), (resc, dm) = plan, ep
+            r = ops.gemm_nt_planes(self.split0(a, k, mode), Bop, n, kp, bias=bias, res_f32=resc, act=act, slope=slope, dmask_f32=dm,
+                                   dmask_act=mask_act if dm is not None else NONE, dmask_slope=slope, out=out, x_order=x_order, planes_out=emit)
+            return self._register_planes(r[0], n, r[1]) if emit else r
         a_op = self.split0(a, k, 1) if swap else self._a(a, k)
-        if (self.bf16 and RANK1 and orient == "nn" and N == 1 and a.dtype == BF16 and res is None and bias is None
+        if (self.bf16 and orient == "nn" and N == 1 and a.dtype == BF16 and res is None and bias is None
                 and mask is not None and mask_act != NONE and not out_f32 and mask.stride(0) % 8 == 0 and mask.shape[1] >= ceil16(K)
                 and ceil16(K) <= 1024):
             # the logit layer's input cotangent: seed (rows,1) x weight row (1,K), masked -- a streaming kernel, not a K = 1 GEMM
@@ -302,21 +288,6 @@ class _Math:
 
     def flush(self):
         """launch the collected weight-gradient contractions (before the optimizer step reads the gradient bucket)"""
-        if (self.tn and TN_PHASED and getattr(self, "_side", None) is not None and len(self.tn) <= ops._lib.TN_GROUP_MAX
-                and all(it[2] <= 256 and it[3] <= 256 for it in self.tn) and not self.tn2
-                and len({it[4].data_ptr() for it in self.tn}) == len(self.tn)):
-            # (layers of at most 256 x 256 with distinct gradient slots only: a wide layer is several blocks of the launch, and
-            # the phased form takes one chunk)
-            # both parts add into the same gradient slots -- but only their SUMS touch the slots: this part's contractions
-            # start now, beside what is left of the side part, and only the sums wait for it
-            ws = ops._tn_group_workspace(self.tn[0][0].device)
-            ops.gemm_tn_group(self.tn, phase=1, workspace=ws, max_workgroups=TN_MAIN_WGS)
-            self.join()
-            ops.gemm_tn_group(self.tn, phase=2, workspace=ws, max_workgroups=TN_MAIN_WGS)
-            self.tn = []
-            self.tn2, self._tn_slots = [], set()
-            self._splits, self._split_src, self._casts = [], [], {}
-            return
         self.join()                          # (both parts accumulate into the same gradient slots: never concurrently)
         if self.tn:
             ops.gemm_tn_group(self.tn)
@@ -340,9 +311,8 @@ class _Math:
         self.tn = []
 
     def join(self):
-        side = getattr(self, "_side", None)
-        if side is not None:
-            torch.cuda.current_stream().wait_stream(side[0])
+        if self._side is not None:
+            torch.cuda.current_stream().wait_stream(self._side[0])
             self._side = None
 
     def can_split(self, B):
@@ -350,13 +320,8 @@ class _Math:
         # (inside a hipGraph capture only on the stream the capture was begun on: hipStreamEndCapture of this HIP release
         # crashes on a fork inside a fork, or on an edge between sibling branches -- a step that runs on a forked stream
         # there, concurrent critics, keeps sweep 4 in one part)
-        return (self.bf16 and TN_SPLIT and TN_GROUP and B % 32 == 0 and ops.tn_group_ok(B, 1, 1, 0)
+        return (self.bf16 and TN_SPLIT and B % 32 == 0 and ops.tn_group_ok(B, 1, 1, 0)
                 and (not torch.cuda.is_current_stream_capturing() or capture_root()))
-
-    def fusable(self, n, k, rows):
-        """the mask (and skip) ride the GEMM epilogue of every bf16 kernel (an element's mask value is read by the thread
-        that then writes that element), so the output may overwrite the mask"""
-        return self.bf16
 
     def outer(self, g, x, N, K, wslot, bslot=None, colsum_rows=None):
         """wslot (N,K) += g^T x;  bslot (N) += column sums of g over rows [0, colsum_rows) (all rows by default; through the
@@ -367,7 +332,7 @@ class _Math:
             narrow = N < 16
             M = gb.shape[0]
             cr = M if colsum_rows is None else colsum_rows
-            if TN_GROUP and ops.tn_group_ok(M, min(N, 256), min(K, 256), cr):
+            if ops.tn_group_ok(M, min(N, 256), min(K, 256), cr):
                 # joins the step's grouped launch (a DenseDim-1000 layer is 4 x 4 blocks of 256 x 256: ops.gemm_tn_group hands it
                 # over whole where the group has blocks enough to fill the card, block by block otherwise; the bias sums ride
                 # with the first column block of every row block)
@@ -382,7 +347,7 @@ class _Math:
         rowm = lambda t: t if (t.dim() == 2 and t.stride(1) == 1) else t.contiguous()      # (row-major, any row pitch)
         gc, xc = rowm(g), rowm(x)
         TM, Np, Kp = self.T * gc.shape[0], ceil16(N), ceil16(K)
-        grouped = TN_GROUP and ops.tn_group_ok(TM, min(N, 256), min(K, 256), 0) and (wslot.data_ptr(), 2) not in self._tn_slots
+        grouped = ops.tn_group_ok(TM, min(N, 256), min(K, 256), 0) and (wslot.data_ptr(), 2) not in self._tn_slots
         # (planes: the grouped launch only, layers of one 256 x 256 block; it reads piece (0 1 0 1 2 0)[t] of g and (0 0 1 1 0 2)[t] of x)
         pa = 2 if (grouped and N <= 256 and K <= 256 and self.planes_ok(N) and self.cached_split(gc, N, 1) is None) else 0
         pb = 1 if (grouped and N <= 256 and K <= 256 and self.planes_ok(K) and self.cached_split(xc, K, 0) is None) else 0
@@ -430,46 +395,38 @@ class _Lin:
         return m.mm(gz, self.W, "nn", res=skip, mask=mask, mask_act=mask_act, slope=slope, out=out, out_f32=out_f32)
 
     def tan(self, m, u, y, skip=None, out=None, inplace=False):
-        """(u W^T + skip) * act'(y): tangent through this layer.  inplace: where the mask rides the GEMM epilogue (or there is
-        no mask) the result overwrites y -- the interpolated rows of an activation buffer then hold its tangent, and the
-        layer's weight gradient is ONE contraction over all 3B rows (see grads)."""
-        if inplace and out is None and (self.act == NONE or m.fusable(self.N, ceil16(self.K), u.shape[0])) and m.bf16:
+        """(u W^T + skip) * act'(y): tangent through this layer.  inplace (bf16): the result overwrites y -- the mask and the skip
+        ride the GEMM epilogue of every bf16 kernel (an element's mask value is read by the thread that then writes that element).
+        The interpolated rows of an activation buffer then hold its tangent, and the layer's weight gradient is ONE contraction
+        over all 3B rows (see grads)."""
+        if inplace and out is None and m.bf16:
             out = y
         return m.mm(u, self.W, "nt", res=skip, mask=y, mask_act=self.act, slope=self.slope, out=out)
 
-    def grads(self, m, gz, x, B2, u, bias_is_zero=False):
-        """dW += gz[:2B]^T x[:2B] + gz[2B:]^T u,  db += colsum(gz[:2B]).  bias_is_zero: the logit layer of a critic step --
-        its cotangent is -1/B on the B real rows and +1/B on the B fake rows, so the bias gradient is EXACTLY zero (the
+    def grads(self, m, gz, x, B2, u, with_bias=True):
+        """dW += gz[:2B]^T x[:2B] + gz[2B:]^T u,  db += colsum(gz[:2B]) if with_bias.  Without: the logit layer of a bf16 critic
+        step -- its cotangent is -1/B on the B real rows and +1/B on the B fake rows, so the bias gradient is EXACTLY zero (the
         reference's two backward passes cancel to the last bit as well; the pairing column-sum kernel reproduced that 0 in
         26 us per step): the slot, zeroed by zero_grad, is left alone"""
-        if bias_is_zero:
-            bz = self.b
-            self.b = None
-            try:
-                return self._grads(m, gz, x, B2, u)
-            finally:
-                self.b = bz
-        return self._grads(m, gz, x, B2, u)
-
-    def grads_part(self, m, g, x, with_bias):
-        """dW += g^T x over the given rows (one part of sweep 4), db += colsum(g) if with_bias"""
-        m.outer(g, x, self.N, self.K, _slot(self.W), self._bslot() if with_bias else None)
-
-    def _grads(self, m, gz, x, B2, u):
+        bslot = self._bslot() if with_bias else None
         if (m.bf16 and x.dtype == BF16 and u.dtype == BF16 and B2 % 128 == 0 and u.data_ptr() == x[B2:].data_ptr()
                 and u.stride(0) == x.stride(0)):
             # the tangent was written over the interpolated rows of x: one launch contracts all 3B rows
-            m.outer(gz, x, self.N, self.K, _slot(self.W), self._bslot(), colsum_rows=B2)
+            m.outer(gz, x, self.N, self.K, _slot(self.W), bslot, colsum_rows=B2)
             return
         if m.bf16 and x.dtype != BF16 and u.dtype != BF16 and B2 % 128 == 0 and x.shape[0] == B2 + u.shape[0]:
             # a network input layer: [x(real, fake); tangent seed] cast into one bf16 operand, one contraction
             xb = torch.empty((x.shape[0], ceil16(self.K)), dtype=BF16, device=x.device)
             ops.cast_pad_bf16(x[:B2], ceil16(self.K), out=xb[:B2])
             ops.cast_pad_bf16(u, ceil16(self.K), out=xb[B2:])
-            m.outer(gz, xb, self.N, self.K, _slot(self.W), self._bslot(), colsum_rows=B2)
+            m.outer(gz, xb, self.N, self.K, _slot(self.W), bslot, colsum_rows=B2)
             return
-        m.outer(gz[:B2], x[:B2], self.N, self.K, _slot(self.W), self._bslot())
+        m.outer(gz[:B2], x[:B2], self.N, self.K, _slot(self.W), bslot)
         m.outer(gz[B2:], u, self.N, self.K, _slot(self.W))
+
+    def grads_part(self, m, g, x, with_bias):
+        """dW += g^T x over the given rows (one part of sweep 4), db += colsum(g) if with_bias"""
+        m.outer(g, x, self.N, self.K, _slot(self.W), self._bslot() if with_bias else None)
 
 
 class _Block:
@@ -498,16 +455,13 @@ class _Block:
         return uh, self.fc2.tan(m, uh, y, skip=u, inplace=True)
 
 
-BLOCK2_STACK = os.environ.get("DHAUG_NO_BLOCK2_STACK") is None
-
-
 def stack_bwd(m, blocks, top, hs, ys):
     """the backward chain through a branch's blocks (last to first): top = cotangent at the last block's fc2 pre-activation;
     hs[i], ys[i]: block i's hidden activation and INPUT.  Returns (a1, a2) with a1[i] = cotangent at block i's fc1
     pre-activation... of fc2's input, a2[i] = cotangent at the pre-activation producing ys[i]; a2[n] = top."""
     n = len(blocks)
     a2, a1 = [None] * n + [top], [None] * n
-    if (BLOCK2_STACK and 2 <= n <= ops._lib.BLOCK2_MAX and all(_pair_ok(m, b.fc2, b.fc1, top, hs[i], ys[i], None) for i, b in enumerate(blocks))):
+    if (2 <= n <= ops._lib.BLOCK2_MAX and all(_pair_ok(m, b.fc2, b.fc1, top, hs[i], ys[i], None) for i, b in enumerate(blocks))):
         # one launch for the whole chain (dhaug_gemm_block2_stack_bf16): block i takes block i + 1's result
         desc = [(A._w_nn(blocks[i].fc2.W, m.prec), A._w_nn(blocks[i].fc1.W, m.prec), hs[i], ys[i], None, None) for i in range(n - 1, -1, -1)]
         outs = ops.gemm_block2_stack(top, desc, RELU, 0.0)
@@ -524,7 +478,7 @@ def stack_tan(m, blocks, u0, hs, ys):
     activations / block OUTPUTS, sign bits attached).  Returns (uh, u): uh[i] = tangent of block i's hidden activation,
     u[i] = tangent of its output."""
     n = len(blocks)
-    ok = BLOCK2_STACK and 2 <= n <= ops._lib.BLOCK2_MAX
+    ok = 2 <= n <= ops._lib.BLOCK2_MAX
     x = u0
     for i, b in enumerate(blocks):
         ok = ok and _pair_ok(m, b.fc1, b.fc2, u0, hs[i], ys[i], ys[i]) and hs[i].data_ptr() != x.data_ptr() and ys[i].data_ptr() != x.data_ptr()
@@ -611,7 +565,7 @@ def step_d2(D, optimizerD, real, fake, alpha, lam, prec=None):
     split = m.can_split(B)
     if split:                                                 # sweep 4, real / fake rows: beside the penalty and the tangent sweep
         for lay, gz, x in ((L[0], gz1, X), (L[1], gz2, d1), (L[2], gz3, d2), (L[3], gz4, d3), (L[4], gzl, d4), (L[5], gzp, dl)):
-            lay.grads_part(m, gz[:B2], x[:B2], lay is not L[5])
+            lay.grads_part(m, gz[:B2], x[:B2], lay is not L[5])      # (the logit layer's bias gradient is exactly zero: _Lin.grads)
         m.flush_side()
     g = L[0].bwd(m, gz1[B2:], None, NONE, 0.0, out_f32=True)                 # (B,32) fp32: dD/dx_hat
     v, pen = ops.gp_penalty(g, 2.0 * lam / B, bf16=m.bf16 and SEED_CASTS)
@@ -632,7 +586,7 @@ def step_d2(D, optimizerD, real, fake, alpha, lam, prec=None):
             lay.grads_part(m, gz[B2:], u, False)
     else:
         for lay, gz, x, u in layers:
-            lay.grads(m, gz, x, B2, u, bias_is_zero=(lay is L[5] and m.bf16))
+            lay.grads(m, gz, x, B2, u, with_bias=not (lay is L[5] and m.bf16))
     m.flush()
     return _finish(optimizerD, logits, pen, B, lam)
 
@@ -717,11 +671,12 @@ def step_branchnet(m, optimizerD, branches, Lm, Mb, Lo, X, rows, lam, feats, inp
     B2, M3 = 2 * B, 3 * B
     nb, Dw = len(branches), branches[0].first.N
     F = feats(X)
+    layer_major = _layer_major(m, branches)
     # ---- 1. forward (the branch outputs land side by side: the concatenation is a buffer, not a copy)
     if fwd is not None:                                      # one fused launch that saves every layer's output (same buffers)
         r = fwd()
         cat, y, h, m0, mh, m1, logits = r["cat"], r["y"], r["h"], r["m0"], r["mh"], r["m1"], r["logits"]
-    elif _layer_major(m, branches):
+    elif layer_major:
         cat = m.empty(M3, nb * Dw, dev)
         y, h = _fwd_layer_major(m, branches, F, cat, Dw)
         m0 = Lm.fwd(m, cat)
@@ -754,24 +709,27 @@ def step_branchnet(m, optimizerD, branches, Lm, Mb, Lo, X, rows, lam, feats, inp
         gz_m1, gz_m0 = Mb.bwd(m, gz_m2, mh, m0)
         gcat = Lm.bwd(m, gz_m0, cat, RELU, 0.0, out=m.empty_blocks(M3, nb, Dw, dev))   # (3B, nb*D): cotangents at every branch's last fc2
     g1, g2, gin = [], [], []
-    if _layer_major(m, branches):
+    if layer_major:
         g1, g2 = _bwd_layer_major(m, branches, gcat, h, y, Dw)
         gin = [br.first.bwd(m, g2[bi][0][B2:], None, NONE, 0.0, out_f32=True) for bi, br in enumerate(branches)]
-    for bi, br in enumerate(branches if not gin else []):
-        # a2[i]: cotangent at the pre-activation producing y[i]
-        a1, a2 = stack_bwd(m, br.blocks, gcat[:, bi * Dw:(bi + 1) * Dw], h[bi], y[bi])
-        g1.append(a1); g2.append(a2)
-        gin.append(br.first.bwd(m, a2[0][B2:], None, NONE, 0.0, out_f32=True))   # (B, w_b) fp32, x_hat rows only
+    else:
+        for bi, br in enumerate(branches):
+            # a2[i]: cotangent at the pre-activation producing y[i]
+            a1, a2 = stack_bwd(m, br.blocks, gcat[:, bi * Dw:(bi + 1) * Dw], h[bi], y[bi])
+            g1.append(a1); g2.append(a2)
+            gin.append(br.first.bwd(m, a2[0][B2:], None, NONE, 0.0, out_f32=True))   # (B, w_b) fp32, x_hat rows only
+    # sweep 4's walk over the layers: (layer, cotangent, input, with_bias).  The logit layer's bias gradient is exactly zero in bf16
+    # (_Lin.grads)
+    layers = []
+    for bi, br in enumerate(branches):
+        layers.append((br.first, g2[bi][0], F[bi], True))
+        for i, blk in enumerate(br.blocks):
+            layers += [(blk.fc1, g1[bi][i], y[bi][i], True), (blk.fc2, g2[bi][i + 1], h[bi][i], True)]
+    layers += [(Lm, gz_m0, cat, True), (Mb.fc1, gz_m1, m0, True), (Mb.fc2, gz_m2, mh, True), (Lo, gzo, m1, not m.bf16)]
     split = m.can_split(B)
     if split:                                                # sweep 4, real / fake rows: beside the penalty and the tangent sweep
-        for bi, br in enumerate(branches):
-            br.first.grads_part(m, g2[bi][0][:B2], F[bi][:B2], True)
-            for i, blk in enumerate(br.blocks):
-                blk.fc1.grads_part(m, g1[bi][i][:B2], y[bi][i][:B2], True)
-                blk.fc2.grads_part(m, g2[bi][i + 1][:B2], h[bi][i][:B2], True)
-        Lm.grads_part(m, gz_m0[:B2], cat[:B2], True)
-        Mb.fc1.grads_part(m, gz_m1[:B2], m0[:B2], True); Mb.fc2.grads_part(m, gz_m2[:B2], mh[:B2], True)
-        Lo.grads_part(m, gzo[:B2], m1[:B2], False)           # (its bias gradient is exactly zero: see _Lin.grads)
+        for lin, gz, x, with_bias in layers:
+            lin.grads_part(m, gz[:B2], x[:B2], with_bias)
         m.flush_side()
     # ---- 3. penalty and tangent sweep (x_hat rows)
     if penalty is not None and m.bf16:
@@ -785,14 +743,15 @@ def step_branchnet(m, optimizerD, branches, Lm, Mb, Lo, X, rows, lam, feats, inp
         T = tangents(v.reshape(g.shape))
         n_pen = gv.shape[0]
     u, uh = [], []
-    if _layer_major(m, branches):
+    if layer_major:
         u_first = [br.first.tan(m, T[bi], ops.tail_rows(y[bi][0], B2), inplace=True) for bi, br in enumerate(branches)]
         u, uh = _tan_layer_major(m, branches, u_first, [[ops.tail_rows(t, B2) for t in h[bi]] for bi in range(nb)],
                                  [[ops.tail_rows(t, B2) for t in y[bi][1:]] for bi in range(nb)])
-    for bi, br in enumerate(branches if not u else []):
-        u_first = br.first.tan(m, T[bi], ops.tail_rows(y[bi][0], B2), inplace=True)
-        uhs, uo = stack_tan(m, br.blocks, u_first, [ops.tail_rows(t, B2) for t in h[bi]], [ops.tail_rows(t, B2) for t in y[bi][1:]])
-        u.append([u_first] + uo); uh.append(uhs)
+    else:
+        for bi, br in enumerate(branches):
+            u_first = br.first.tan(m, T[bi], ops.tail_rows(y[bi][0], B2), inplace=True)
+            uhs, uo = stack_tan(m, br.blocks, u_first, [ops.tail_rows(t, B2) for t in h[bi]], [ops.tail_rows(t, B2) for t in y[bi][1:]])
+            u.append([u_first] + uo); uh.append(uhs)
     if all(u[bi][-1].data_ptr() == cat[B2:, bi * Dw:].data_ptr() for bi in range(nb)):
         ucat = cat[B2:]                                      # every branch tangent was written in place
     else:
@@ -810,24 +769,17 @@ def step_branchnet(m, optimizerD, branches, Lm, Mb, Lo, X, rows, lam, feats, inp
         um0 = Lm.tan(m, ucat, m0[B2:], inplace=True)
         umh, um1 = Mb.tan(m, um0, mh[B2:], m1[B2:])
     # ---- 4. weight / bias gradients (the interpolated rows' part where the real / fake rows' part is already under way)
-    if split:
-        for bi, br in enumerate(branches):
-            br.first.grads_part(m, g2[bi][0][B2:], T[bi], False)
-            for i, blk in enumerate(br.blocks):
-                blk.fc1.grads_part(m, g1[bi][i][B2:], u[bi][i], False)
-                blk.fc2.grads_part(m, g2[bi][i + 1][B2:], uh[bi][i], False)
-        Lm.grads_part(m, gz_m0[B2:], ucat, False)
-        Mb.fc1.grads_part(m, gz_m1[B2:], um0, False); Mb.fc2.grads_part(m, gz_m2[B2:], umh, False)
-        Lo.grads_part(m, gzo[B2:], um1, False)
-    else:
-        for bi, br in enumerate(branches):
-            br.first.grads(m, g2[bi][0], F[bi], B2, T[bi])
-            for i, blk in enumerate(br.blocks):
-                blk.fc1.grads(m, g1[bi][i], y[bi][i], B2, u[bi][i])
-                blk.fc2.grads(m, g2[bi][i + 1], h[bi][i], B2, uh[bi][i])
-        Lm.grads(m, gz_m0, cat, B2, ucat)
-        Mb.fc1.grads(m, gz_m1, m0, B2, um0); Mb.fc2.grads(m, gz_m2, mh, B2, umh)
-        Lo.grads(m, gzo, m1, B2, um1, bias_is_zero=m.bf16)
+    tans = []                                                # the tangents of the layers' inputs, in the order of `layers`
+    for bi, br in enumerate(branches):
+        tans.append(T[bi])
+        for i in range(len(br.blocks)):
+            tans += [u[bi][i], uh[bi][i]]
+    tans += [ucat, um0, umh, um1]
+    for (lin, gz, x, with_bias), t in zip(layers, tans):
+        if split:
+            lin.grads_part(m, gz[B2:], t, False)
+        else:
+            lin.grads(m, gz, x, B2, t, with_bias=with_bias)
     m.flush()
     return _finish(optimizerD, logits, pen, n_pen, lam, rows=B)
 

@@ -64,9 +64,7 @@ struct TnLayer {
 };
 struct TnGroup {
     int nlayers;
-    int abl;                        // development: 1 no partial stores, 2 no fragment reads / MFMAs, 4 no copies (timing only);
-                                    // bit 8 (set by the host for the two-phase form): a block's only workgroup writes a partial
-                                    // result too -- in that form only the summing launch may touch the gradient slots
+    int abl;                        // development: 1 no partial stores, 2 no fragment reads / MFMAs, 4 no copies (timing only)
     float* ws;
     TnLayer L[T2_MAX_LAYERS];
 };
@@ -211,7 +209,7 @@ __global__ __launch_bounds__(512, 1) void gemm_tn_group_kernel(TnGroup grp_by_va
     }
     if (!live || (abl & 1)) return;
     // (D[n1][n2]: the lane owns column n2 = lane & 31 of its tile, rows n1 = (r & 3) + 8 (r >> 2) + 4 (lane >> 5))
-    if (split == 1 && !(abl & 8)) {
+    if (split == 1) {
         // the block's only workgroup: its result IS the block's -- added into (or stored to) the gradient slot right here,
         // 128-byte row pieces; no partial result, nothing for the summing launch to do
         float* C = L->C + (long long)256 * bi * L->ldc + 256 * bj;
@@ -282,8 +280,7 @@ __global__ __launch_bounds__(256) void tn_group_reduce_kernel(TnGroup g) {
     float* ws = *(float* const __attribute__((address_space(4)))*)(ka + __builtin_offsetof(TnGroup, ws));
     LayerPtr L = (LayerPtr)(ka + __builtin_offsetof(TnGroup, L)) + blockIdx.y;
     (void)g;
-    const int abl = *(const int __attribute__((address_space(4)))*)(ka + __builtin_offsetof(TnGroup, abl));
-    if (L->split == 1 && !(abl & 8)) return;                      // (its workgroups wrote the gradient slot themselves)
+    if (L->split == 1) return;                      // (its workgroups wrote the gradient slot themselves)
     const int n1 = L->n1, n2 = L->n2, nwg = L->nwg, acc = L->accumulate & 1;   // (split > 1: a single block, n1, n2 <= 256)
     const float* p0 = ws + (long long)L->ws0 * T2_WS_STRIDE;
     float* C = L->C;
@@ -323,14 +320,7 @@ static_assert(DHAUG_TN_GROUP_WORKSPACE_FLOATS == (long long)T2_MAX_WG * T2_WS_ST
 static_assert(sizeof(TnGroup) <= 4096, "the group travels as a kernel argument");
 
 /* see include/dhaug.h */
-int dhaug_gemm_tn_group_bf16_phase(const dhaug_tn_layer* layers, int n, float* workspace, int phase, void* stream);
-
 int dhaug_gemm_tn_group_bf16(const dhaug_tn_layer* layers, int n, float* workspace, void* stream) {
-    return dhaug_gemm_tn_group_bf16_phase(layers, n, workspace, 0, stream);
-}
-
-int dhaug_gemm_tn_group_bf16_phase(const dhaug_tn_layer* layers, int n, float* workspace, int phase, void* stream) {
-    DHAUG_CHECK(phase >= 0 && phase <= 2, DHAUG_EINVAL);
     DHAUG_CHECK(n >= 0 && n <= T2_MAX_LAYERS, DHAUG_EINVAL);
     if (n == 0) return DHAUG_OK;
     DHAUG_CHECK_PTR(layers); DHAUG_CHECK_PTR(workspace);
@@ -421,27 +411,20 @@ int dhaug_gemm_tn_group_bf16_phase(const dhaug_tn_layer* layers, int n, float* w
     // the group has blocks enough without splitting; a long batch of few wide layers goes block by block)
     int wg = 0, slot = 0;
     for (int i = 0; i < n; ++i) {
-        DHAUG_CHECK(nblk[i] == 1 || phase == 0, DHAUG_EUNSUPPORTED);      // (a wide layer's blocks have no summing pass)
         g.L[i].wg0 = wg; g.L[i].nwg = nblk[i] * g.L[i].split; wg += g.L[i].nwg;
         g.L[i].ws0 = slot;
-        if (g.L[i].split > 1 || phase != 0) slot += g.L[i].nwg;
+        if (g.L[i].split > 1) slot += g.L[i].nwg;
     }
-    if (phase != 0) g.abl |= 8;
     DHAUG_CHECK(slot <= T2_MAX_WG, DHAUG_EUNSUPPORTED);
     (void)blocks;
     static const bool xcd_deal = getenv("DHAUG_TN_NO_XCD_DEAL") == nullptr;
     if (wide && xcd_deal) { g.abl |= 16; wg = (wg + 7) & ~7; }     // (workgroups beyond the last layer's range return at once)
     hipStream_t s = (hipStream_t)stream;
-    // phase 1: the partial results only; phase 2: only their sums into the gradient slots (the same dealing, recomputed from
-    // the same descriptors); 0: both
-    if (phase != 2) {
-        if (const int e = dhaug_dynamic_lds<gemm_tn_group_kernel>(T2_LDS)) return e;
-        hipLaunchKernelGGL(gemm_tn_group_kernel, dim3((unsigned)wg), dim3(512), T2_LDS, s, g);
-        int rc = dhaug_launch_status();
-        if (rc != DHAUG_OK || phase == 1) return rc;
-    }
+    if (const int e = dhaug_dynamic_lds<gemm_tn_group_kernel>(T2_LDS)) return e;
+    hipLaunchKernelGGL(gemm_tn_group_kernel, dim3((unsigned)wg), dim3(512), T2_LDS, s, g);
+    if (const int rc = dhaug_launch_status()) return rc;
     // (nothing to sum where every block had one workgroup that added its result into the slot itself: a video step's wide layers)
-    bool sums = phase != 0;
+    bool sums = false;
     for (int i = 0; i < n; ++i) sums = sums || g.L[i].split > 1;
     if (!sums) return DHAUG_OK;
     hipLaunchKernelGGL(tn_group_reduce_kernel, dim3(256, (unsigned)n), dim3(256), 0, s, g);

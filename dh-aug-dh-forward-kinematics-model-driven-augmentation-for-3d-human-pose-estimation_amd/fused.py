@@ -6,7 +6,6 @@ changes (the optimizer step invalidates the cache).  Used for the no-grad passes
 (model_fk_gan_train.py:305-308 `.data`), the flipped critic evaluations of the G step (:463-468) and inference.
 Same arithmetic as the layer-by-layer bf16 path (bf16 operands, fp32 accumulate, bf16 activations)."""
 import ctypes
-import os
 
 import torch
 
@@ -21,7 +20,6 @@ _vp = ctypes.c_void_p
 # 1e-4 logit tolerance against the fp32 reference)
 MODES = ("bf16", "f16x3")
 X3_WORKSPACE_BYTES = 2 * 256 * 4 * 64 * 128 * 4               # DHAUG_MLP_X3_WORKSPACE_BYTES of include/dhaug.h
-SIGN_BITS = os.environ.get("DHAUG_NO_SIGN_BITS") is None      # forward-with-save also emits (y > 0) bit arrays of its run layers
 
 
 def supported(*dims):
@@ -84,8 +82,8 @@ def _unit(kind, flags=0, src=-1, dst=-1, res=-1, src2=-1, ksteps2=0, ksteps=0, n
         # rows [0, save_rows) only (0: all, < 0: none) -- honoured only where the sign bits are written too: whoever asks for
         # fewer rows reads the other rows' masks from the bits
         # (or where the layer has no activation -- `unmasked`: no mask is ever read from its image)
-        u.save_rows = int(save_rows) if ((bits and SIGN_BITS) or unmasked) else 0
-        if bits and SIGN_BITS:
+        u.save_rows = int(save_rows) if (bits or unmasked) else 0
+        if bits:
             # the layer also leaves (y > 0) as one bit per element (struct dhaug_mlp_unit.bits): the backward / tangent sweeps
             # read that instead of the bf16 image (critic_step.py); the array rides on the saved tensor
             save._dhaug_bits = new_bits(save.shape[0], save.device)
@@ -417,10 +415,9 @@ def critic2d_forward_save(D, x, save_rows=0):
 def partial_save_ok(rows):
     """may a step whose batch is made of `rows`-row parts (real | fake | interpolated; or the G step's one part) ask the
     forward-with-save programs to leave some parts' block-layer images unwritten?  Only if every consumer of those rows' masks
-    reads the sign bits: bits written and consumed, and every part -- hence every launch over 1, 2 or 3 parts -- made of whole
-    32-row tiles (a launch over rows that are not is served by the kernels that read the mask IMAGE)"""
-    from . import ops
-    return SIGN_BITS and ops.DBITS and rows > 0 and rows % 32 == 0
+    reads the sign bits: every part -- hence every launch over 1, 2 or 3 parts -- made of whole 32-row tiles (a launch over
+    rows that are not is served by the kernels that read the mask IMAGE)"""
+    return rows > 0 and rows % 32 == 0
 
 
 def generator_head(G, z, mode="bf16"):

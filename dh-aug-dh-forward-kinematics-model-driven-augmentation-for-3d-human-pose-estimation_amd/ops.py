@@ -643,7 +643,7 @@ def gemm_nt_dmask(A, B, N, K, dmask, dmask_act, dmask_slope=0.0, res_bf16=None, 
         out = torch.empty((M, ceil_to(N, 16)), dtype=BF16, device=A.device)
     assert out.dtype == BF16 and out.stride(1) == 1 and out.shape[0] == M and out.shape[1] >= N
     cols = getattr(dmask, "_dhaug_bits_cols", None)
-    if (cols is not None and DBITS and N == 256 * len(cols) and len(cols) <= 2 and K in (16, 32, 48, 64, 112, 128, 256) and res_bf16 is None
+    if (cols is not None and N == 256 * len(cols) and len(cols) <= 2 and K in (16, 32, 48, 64, 112, 128, 256) and res_bf16 is None
             and dmask_act != 0 and M > 0 and A.stride(0) % 8 == 0 and out.stride(0) % 8 == 0):
         # a wide output whose 256-column blocks carry their own sign bits (the cotangent of the 3D critic's concatenation)
         assert all(c.device == A.device for c in cols), "sign bits must live on the operands' device"
@@ -652,13 +652,13 @@ def gemm_nt_dmask(A, B, N, K, dmask, dmask_act, dmask_slope=0.0, res_bf16=None, 
         return out
     bits = getattr(dmask, "_dhaug_bits", None)
     assert bits is None or bits.device == A.device, "sign bits must live on the operands' device"
-    if (bits is not None and DBITS and N == 256 and K in (16, 32, 48, 64, 112, 128) and res_bf16 is None and dmask_act != 0
+    if (bits is not None and N == 256 and K in (16, 32, 48, 64, 112, 128) and res_bf16 is None and dmask_act != 0
             and M > 0 and M % 32 == 0 and A.stride(0) % 8 == 0 and out.stride(0) % 8 == 0):
         # a 256-wide layer behind a NARROW one (the tangent through a branch's first layer): the same mask bits, K < 256
         _lib.call("dhaug_gemm_bf16_dbits_wide", _p(A), A.stride(0), _p(B), B.stride(0), _p(bits), 0, dmask_act, float(dmask_slope),
                   _p(out), out.stride(0), M, N, K, _stream())
         return out
-    if (bits is not None and DBITS and N == 256 and K == 256 and M % 32 == 0 and M > 0 and dmask_act != 0
+    if (bits is not None and N == 256 and K == 256 and M % 32 == 0 and M > 0 and dmask_act != 0
             and A.stride(0) % 8 == 0 and out.stride(0) % 8 == 0):
         # the mask as the sign-bit array its forward-with-save layer left beside the image: 32 bytes per row instead of 512
         _lib.call("dhaug_gemm_bf16_dbits", _p(A), A.stride(0), _p(B), B.stride(0), _p(res_bf16),
@@ -725,13 +725,12 @@ def gemm_nt_dmask_f32(A, B, N, K, dmask, dmask_act, dmask_slope=0.0, res_f32=Non
     return out
 
 
-DBITS = os.environ.get("DHAUG_NO_DBITS") is None          # consume sign-bit masks where a saved activation carries one
 BLOCK2 = os.environ.get("DHAUG_NO_BLOCK2") is None        # the two layers of a residual block's backward / tangent step in one launch
 
 
 def block2_ok(x, mask1, mask2, M):
     """can dhaug_gemm_block2_bf16 take this pair of 256 -> 256 layers?  (bf16 rows, whole 32-row tiles, both masks as sign bits)"""
-    return (BLOCK2 and DBITS and M > 0 and M % 32 == 0 and x.dtype == BF16 and x.shape[1] >= 256 and x.stride(0) % 8 == 0
+    return (BLOCK2 and M > 0 and M % 32 == 0 and x.dtype == BF16 and x.shape[1] >= 256 and x.stride(0) % 8 == 0
             and getattr(mask1, "_dhaug_bits", None) is not None and getattr(mask2, "_dhaug_bits", None) is not None)
 
 
@@ -839,12 +838,10 @@ def tn_group_ok(M, N1, N2, colsum_rows):
 TN_WIDE_MIN_BLOCKS = int(os.environ.get("DHAUG_TN_WIDE_MIN_BLOCKS", "128"))
 
 
-def gemm_tn_group(items, max_workgroups=0, phase=0, workspace=None):
+def gemm_tn_group(items, max_workgroups=0):
     """items: [(A, B, N1, N2, out, colsum | None, colsum_rows, accumulate, M | None, lda | None, ldb | None)] -- the weight
     gradients C_i (+)= A_i^T B_i of several layers in one launch (+ one that sums the partial results).
-    max_workgroups: leave CUs to kernels running beside this launch (0: one workgroup per CU).
-    phase 1: the contractions only (partial results into `workspace`); phase 2: only their sums into the outputs (same items,
-    same workspace; one chunk of at most TN_GROUP_MAX items); 0: both."""
+    max_workgroups: leave CUs to kernels running beside this launch (0: one workgroup per CU)."""
     # layers wider than 256: whole ("wide": one workgroup per 256 x 256 block, which adds into the gradient slot itself) where the
     # chunk they travel in has blocks enough to fill the card without splitting any over the batch; as 256 x 256 blocks, each an
     # item of its own, otherwise (a long batch of few wide layers: the blocks are split over the batch and summed)
@@ -855,7 +852,7 @@ def gemm_tn_group(items, max_workgroups=0, phase=0, workspace=None):
         flat = []
         for i0 in range(0, len(items), _lib.TN_GROUP_MAX):
             chunk = items[i0:i0 + _lib.TN_GROUP_MAX]
-            if phase == 0 and sum(nblk(it) for it in chunk) >= TN_WIDE_MIN_BLOCKS:
+            if sum(nblk(it) for it in chunk) >= TN_WIDE_MIN_BLOCKS:
                 flat.extend(chunk)
                 continue
             for (A, B, N1, N2, out, cs, cr, accumulate, M, la, lb, pa, pb) in chunk:
@@ -866,7 +863,6 @@ def gemm_tn_group(items, max_workgroups=0, phase=0, workspace=None):
                         flat.append((A[:, n0:], B[:, k0:], min(256, N1 - n0), min(256, N2 - k0), out[n0:, k0:], c,
                                      cr if c is not None else 0, accumulate, A.shape[0] if M is None else M, la, lb, pa, pb))
         items = flat
-    assert phase == 0 or (len(items) <= _lib.TN_GROUP_MAX and workspace is not None)
     # the items of ONE launch are summed into their outputs concurrently (a block that is left with one workgroup adds its
     # result into C / colsum with a plain read-modify-write): two items with the same output must not share a launch
     # (include/dhaug.h, dhaug_gemm_tn_group_bf16).  A later contribution to an output waits for a launch of its own.
@@ -880,10 +876,8 @@ def gemm_tn_group(items, max_workgroups=0, phase=0, workspace=None):
             seen |= keys
             first.append(it)
     if later:
-        if phase != 0:
-            raise RuntimeError("gemm_tn_group: two items of a phased launch share an output")
-        gemm_tn_group(first, max_workgroups, 0, workspace)
-        gemm_tn_group(later, max_workgroups, 0, workspace)
+        gemm_tn_group(first, max_workgroups)
+        gemm_tn_group(later, max_workgroups)
         return
     for i0 in range(0, len(items), _lib.TN_GROUP_MAX):
         chunk = items[i0:i0 + _lib.TN_GROUP_MAX]
@@ -895,8 +889,7 @@ def gemm_tn_group(items, max_workgroups=0, phase=0, workspace=None):
             d.C, d.ldc, d.colsum_a, d.colsum_rows = _p(out), out.stride(0), _p(cs), cr
             d.M, d.N1, d.N2, d.accumulate = A.shape[0] if M is None else M, N1, N2, int(bool(accumulate))
             d.max_workgroups = int(max_workgroups)
-        ws = workspace if workspace is not None else _tn_group_workspace(chunk[0][0].device)
-        _lib.call("dhaug_gemm_tn_group_bf16_phase", arr, len(chunk), _p(ws), int(phase), _stream())
+        _lib.call("dhaug_gemm_tn_group_bf16", arr, len(chunk), _p(_tn_group_workspace(chunk[0][0].device)), _stream())
 
 
 def gemm_tn(A, B, N1, N2, out=None, accumulate=False, M=None, lda=None, ldb=None, colsum=None, colsum_rows=None):
@@ -1032,7 +1025,7 @@ def rank1_mask(seed, w_col, mask, n, act, slope=0.0, out=None):
     if out is None:
         out = torch.empty((M, ceil_to(n, 16)), dtype=BF16, device=mask.device)
     bits = getattr(mask, "_dhaug_bits", None)
-    if bits is not None and DBITS and n == 256 and act != 0 and out.stride(0) % 8 == 0 and out.shape[1] >= 256:
+    if bits is not None and n == 256 and act != 0 and out.stride(0) % 8 == 0 and out.shape[1] >= 256:
         assert bits.device == out.device, "sign bits must live on the operands' device"
         _lib.call("dhaug_rank1_bits_bf16", _p(seed), seed.stride(0), _p(w_col), w_col.stride(0), _p(bits), _p(out), out.stride(0), M,
                   act, float(slope), _stream())

@@ -467,7 +467,7 @@ int dhaug_gemm_bf16_group(const dhaug_gemm_desc* members, int n, void* stream);
 /* The weight / bias gradients of ALL layers of a critic step in one launch (+ one small launch that sums the partial
  * results): layer i computes C[N1,N2] (+)= A[M,N1]^T * B[M,N2] and colsum_a[N1] (+)= column sums of A over rows
  * [0, colsum_rows), M and colsum_rows multiples of 32, operands bf16 with rows readable up to ceil8(N) columns (of every
- * 256-column block).  N1, N2 <= 256, or "wide" (up to 4096: a grid of 256 x 256 blocks, one workgroup each, phase 0 only -- for
+ * 256-column block).  N1, N2 <= 256, or "wide" (up to 4096: a grid of 256 x 256 blocks, one workgroup each -- for
  * groups that have blocks enough to fill the card without splitting any over the batch: the DenseDim-1000 layers of a video step).
  * A block that ends up with ONE workgroup adds its result into C / colsum_a itself (no partial result, no sum).  One workgroup per CU owns a layer's WHOLE output over its slice of the batch (every operand byte crosses
  * L2 -> LDS once; the 64 x 64-tile kernel behind dhaug_gemm_tn_bf16 re-reads each row four times); the workgroups are dealt
@@ -500,11 +500,6 @@ typedef struct dhaug_tn_layer {
                                    the bytes (the "bf16x6" weight gradients, autograd_ops._raw_outer).  M % 6 == 0 then. */
 } dhaug_tn_layer;
 int dhaug_gemm_tn_group_bf16(const dhaug_tn_layer* layers, int n, float* workspace, void* stream);
-/* The same in two calls: phase 1 launches the contractions (partial results into `workspace`), phase 2 the sums into the
- * gradient slots -- same `layers`, same `workspace`; phase 0 = both.  Only the sums touch C / colsum_a, so the contractions
- * of one part of a step may run beside another part's (R/models_Fk_GAN/model_fk_gan_train.py:191-214: the three backward
- * passes of a critic step add into the same .grad). */
-int dhaug_gemm_tn_group_bf16_phase(const dhaug_tn_layer* layers, int n, float* workspace, int phase, void* stream);
 
 /* fp32 -> bf16 (round-to-nearest-even) with zero padding: src (rows, cols) ld_src -> dst (rows, ld_dst),
  * columns [cols, pad_cols) zero-filled.  Used to pack weights / inputs as GEMM operands. */

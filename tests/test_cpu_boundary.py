@@ -257,6 +257,37 @@ def test_product_never_imports_the_oracle():
                 assert "oracle" not in src, os.path.join(d, f)
 
 
+def test_environment_switches_are_documented():
+    """every DHAUG_* variable the package's Python modules read has a row in INTEGRATION.md's table, and the retired switches
+    (spelt here without their prefix, so that this file passes its own scan) are named by no source file any more"""
+    pkg = os.path.join(ROOT, "dh-aug-dh-forward-kinematics-model-driven-augmentation-for-3d-human-pose-estimation_amd")
+    doc = open(os.path.join(ROOT, "INTEGRATION.md")).read()
+    read = set()
+    for d, _, files in os.walk(pkg):
+        for f in files:
+            if f.endswith(".py"):
+                read |= set(re.findall(r"environ\.get\(\s*[\"'](DHAUG_[A-Z0-9_]+)[\"']", open(os.path.join(d, f)).read()))
+    assert len(read) >= 20 and "DHAUG_NO_TN_SPLIT" in read, sorted(read)      # (the scan found the reads)
+    missing = sorted(n for n in read if not re.search(r"\| `%s` \|" % n, doc))
+    assert not missing, "INTEGRATION.md's switch table does not list %s" % missing
+    retired = ["DHAUG_" + n for n in ("TN_PHASED", "TN_MAIN_WGS", "PARTITION", "CU_SHARES", "NO_TN_GROUP", "NO_RANK1", "NO_SPLIT_CACHE",
+                                      "NO_BLOCK2_STACK", "NO_DBITS", "NO_SIGN_BITS")]
+    pat = re.compile(r"\b(%s)\b" % "|".join(retired))
+    tops = [pkg] + [os.path.join(ROOT, t) for t in ("include", "tests", "tools", "oracle")]
+    paths = [os.path.join(ROOT, f) for f in os.listdir(ROOT)]
+    for t in tops:
+        for d, dirs, files in os.walk(t):
+            dirs[:] = [x for x in dirs if x not in ("_ref", "_build", "__pycache__")]      # (built, not source)
+            paths += [os.path.join(d, f) for f in files]
+    n = 0
+    for p in paths:
+        if p.endswith((".py", ".hip", ".h", ".sh")) and os.path.isfile(p):
+            n += 1
+            hit = pat.search(open(p, errors="replace").read())
+            assert hit is None, "%s still names %s" % (p, hit.group(1))
+    assert n > 100
+
+
 def test_module_state_dict_keys_and_host_logic(built):
     """module construction, state_dict key parity with the reference, config defaults: all host-side"""
     import golden_util as GU

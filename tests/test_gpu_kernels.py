@@ -564,7 +564,7 @@ def test_gemm_tn_group_same_output_twice(ops):
         d.A, d.lda, d.B, d.ldb, d.C, d.ldc, d.colsum_a, d.colsum_rows = A.data_ptr(), 256, B.data_ptr(), 256, o.data_ptr(), 256, c.data_ptr(), cr
         d.M, d.N1, d.N2, d.accumulate, d.max_workgroups = A.shape[0], 256, 256, 1, 0
     ws = ops._tn_group_workspace(out.device)
-    rc = lib.lib().dhaug_gemm_tn_group_bf16_phase(arr, 2, ctypes.c_void_p(ws.data_ptr()), 0, ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
+    rc = lib.lib().dhaug_gemm_tn_group_bf16(arr, 2, ctypes.c_void_p(ws.data_ptr()), ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
     assert rc != 0
 
 

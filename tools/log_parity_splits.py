@@ -24,7 +24,7 @@ def spy(name, *a):
     elif name.startswith("dhaug_gemm"):
         if name == "dhaug_gemm_bf16x6_planes":
             log["%s M %d N %d kp %d planes_out %s" % (name, a[14], a[15], a[16], bool(a[12]))] += 1
-        elif name == "dhaug_gemm_tn_group_bf16_phase":
+        elif name == "dhaug_gemm_tn_group_bf16":
             arr, n = a[0], a[1]
             for i in range(n):
                 log["tn item M %d N1 %d N2 %d planes %d %d" % (arr[i].M, arr[i].N1, arr[i].N2, arr[i].planes_a, arr[i].planes_b)] += 1

@@ -1,4 +1,4 @@
-"""Development aid: what each grouped weight-gradient launch (ops.gemm_tn_group -> dhaug_gemm_tn_group_bf16_phase) of ONE eager video
+"""Development aid: what each grouped weight-gradient launch (ops.gemm_tn_group -> dhaug_gemm_tn_group_bf16) of ONE eager video
 iteration (B = 512 x R = 9, DenseDim 1000) is made of: per call of the C entry point the layers' (M, N1, N2), their 256 x 256 blocks, and the
 stream; then each call timed alone on an idle card."""
 import os, sys, argparse, time, ctypes
@@ -36,19 +36,19 @@ torch.cuda.synchronize()
 log = []
 real = _lib.call
 def spy(name, *a):
-    if name == "dhaug_gemm_tn_group_bf16_phase":
-        arr, n, ws, phase, stream = a
+    if name == "dhaug_gemm_tn_group_bf16":
+        arr, n, ws, stream = a
         layers = [(arr[i].M, arr[i].N1, arr[i].N2, int(arr[i].colsum_a is not None), arr[i].max_workgroups) for i in range(n)]
         keep = (_lib.TnLayer * n)()
         ctypes.memmove(keep, arr, ctypes.sizeof(_lib.TnLayer) * n)
-        log.append((layers, phase, stream, keep, n, ws))
+        log.append((layers, stream, keep, n, ws))
     return real(name, *a)
 _lib.call = spy
 V.video_gan_iteration(av, mv, v3, cpv, v2, ["S1"], sv, None, do_g_step=False, camera=(quat, trans, cam9))
 torch.cuda.synchronize()
 _lib.call = real
 tot = 0.0
-for layers, phase, stream, keep, n, ws in log:
+for layers, stream, keep, n, ws in log:
     nb = sum(((l[1] + 255) // 256) * ((l[2] + 255) // 256) for l in layers)
     stages = sum(((l[1] + 255) // 256) * ((l[2] + 255) // 256) * (l[0] // 32) for l in layers)
     flops = sum(2.0 * l[0] * l[1] * l[2] for l in layers)
@@ -56,10 +56,10 @@ for layers, phase, stream, keep, n, ws in log:
     torch.cuda.synchronize()
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     st = torch.cuda.current_stream().cuda_stream
-    real("dhaug_gemm_tn_group_bf16_phase", keep, n, ws, phase, st)
+    real("dhaug_gemm_tn_group_bf16", keep, n, ws, st)
     e0.record()
     for _ in range(5):
-        real("dhaug_gemm_tn_group_bf16_phase", keep, n, ws, phase, st)
+        real("dhaug_gemm_tn_group_bf16", keep, n, ws, st)
     e1.record()
     torch.cuda.synchronize()
     us = e0.elapsed_time(e1) * 200.0
@@ -67,7 +67,7 @@ for layers, phase, stream, keep, n, ws in log:
     shapes = {}
     for l in layers:
         shapes[l[:3]] = shapes.get(l[:3], 0) + 1
-    print("phase %d layers %2d blocks %4d stages %7d  %.1f GF  alone %7.1f us = %.2f of the MFMA peak  cap %d  %s" % (
-        phase, len(layers), nb, stages, flops / 1e9, us, flops / (us * 1e-6) / 2.5e15, layers[0][4],
+    print("layers %2d blocks %4d stages %7d  %.1f GF  alone %7.1f us = %.2f of the MFMA peak  cap %d  %s" % (
+        len(layers), nb, stages, flops / 1e9, us, flops / (us * 1e-6) / 2.5e15, layers[0][4],
         " ".join("%dx(%d,%d,%d)" % (c, *k) for k, c in sorted(shapes.items()))))
 print("calls %d, alone in total %.1f us" % (len(log), tot))
