@@ -408,6 +408,37 @@ def test_gemm_routes(built):
     assert not bad, bad
 
 
+def test_gemm_case_table_reaches_every_route(built):
+    """tests/gemm_cases.py means what it says: every record of the table tests/test_gpu_gemm_routes.py runs is routed, by the very
+    functions the dispatchers call, to the kernel and KSTEPS it names (a record whose route does not read dhaug_p8_supported() gets
+    the same answer for either value), and the table as a whole reaches every NT kernel, every instantiation of the two templated
+    ones, and both TN kernels."""
+    import gemm_cases as G
+    lib = ctypes.CDLL(os.path.join(ROOT, "tests", "hostcheck", "_build", "libhostcheck.so"))
+    LL = ctypes.c_longlong
+    lib.hostcheck_nt_route.argtypes = [LL] * 4 + [ctypes.c_int] * 9 + [LL]
+    lib.hostcheck_tn_route.argtypes = [LL] * 3
+    bad, seen_nt, seen_tn = [], set(), set()
+    for c in G.NT_CASES:
+        assert set(k for k, _ in c.env) <= set(G.SWITCHES)
+        for p8_ok in ((False, True) if c.p8_ok is None else (c.p8_ok,)):
+            r = lib.hostcheck_nt_route(*c.route_args(p8_ok))
+            got = (G.NT_KERNELS[r // 100], r % 100)
+            if got != (c.kernel, c.ksteps):
+                bad.append((c.ident, p8_ok, got))
+        seen_nt.add((c.kernel, c.ksteps))
+    for c in G.TN_CASES:
+        got = G.TN_KERNELS[lib.hostcheck_tn_route(c.M, c.N1, c.N2)]
+        if got != c.kernel:
+            bad.append((c.ident, got))
+        seen_tn.add(c.kernel)
+    assert not bad, bad
+    assert set(k for k, _ in seen_nt) == set(G.NT_KERNELS) and len(G.NT_KERNELS) == 9
+    assert set(ks for k, ks in seen_nt if k == "WS") == set(G.WS_KSTEPS) == {1, 2, 3, 4, 7, 8, 16}
+    assert set(ks for k, ks in seen_nt if k == "NT256S") == set(G.NT256S_KSTEPS) == {8, 16}
+    assert seen_tn == set(G.TN_KERNELS) and len(G.TN_KERNELS) == 2
+
+
 def test_hostcheck_under_address_and_ub_sanitizers(built, tmp_path):
     """the same host build as an executable under -fsanitize=address,undefined (-fno-sanitize-recover): ordinary poses and
     the degenerate ones of tests/test_gpu_edge.py (angles of +-1e4 and +-1e7 degrees -- the library path of the range
