@@ -98,7 +98,7 @@ class MlpUnit(ctypes.Structure):
 class WfragDesc(ctypes.Structure):
     """struct dhaug_wfrag_desc (include/dhaug.h)"""
     _fields_ = [("W", _vp), ("ldw", _i64), ("dst", _vp), ("bias", _vp), ("bias_dst", _vp), ("dot_dst", _vp), ("N", _i32),
-                ("K", _i32), ("k0", _i32), ("ksteps", _i32)]
+                ("K", _i32), ("k0", _i32), ("ksteps", _i32), ("W2", _vp), ("bias2", _vp), ("ldw2", _i64), ("K2", _i32), ("pad_", _i32)]
 
 
 class RepackDesc(ctypes.Structure):
@@ -149,6 +149,7 @@ TN_GROUP_WORKSPACE_FLOATS = 256 * (256 * 256 + 256)
 SIGNATURES["dhaug_gemm_tn_group_bf16"] = [ctypes.POINTER(TnLayer), _i32, _vp, _vp]
 SIGNATURES["dhaug_pack_wfrag"] = [_vp, _i64, _vp, _i64, _i64, _i64, _vp]
 SIGNATURES["dhaug_pack_wfrag_batch"] = [_vp, _i32, _vp]
+SIGNATURES["dhaug_pack_wfrag_composed"] = [_vp, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _vp]
 SIGNATURES["dhaug_mlp_forward"] = [ctypes.POINTER(MlpUnit), _i32, _i64, _vp]
 SIGNATURES["dhaug_pack_wfrag_f16x2"] = [_vp, _i64, _vp, _i64, _i64, _i64, _vp]
 SIGNATURES["dhaug_pack_wfrag_f16x2_t16"] = [_vp, _i64, _vp, _i64, _i64, _i64, _vp]

@@ -1412,10 +1412,34 @@ __global__ __launch_bounds__(256) void pack_wfrag_kernel(const float* __restrict
     }
 }
 
-// the same for every layer of a network in ONE launch (after an optimizer step): blockIdx.y = descriptor.  Also refreshes the
-// zero-padded fp32 bias [256] and, for a logit layer folded into its producer, the DOT_OUT vector [257].
-__global__ __launch_bounds__(256) void pack_wfrag_batch_kernel(const dhaug_wfrag_desc* __restrict__ descs) {
-    const dhaug_wfrag_desc d = descs[blockIdx.y];
+// element (n, k) of the layer a descriptor stands for: W[n][k0 + k], or, with a second operand, of the composite of two
+// linear layers with nothing between them, (W * W2)[n][k0 + k] = sum over m < K2 of W[n][m] W2[m][k0 + k] -- formed from the
+// fp32 parameters, accumulated in fp64 in the order of m, rounded to bf16 by the caller (neither factor is rounded on its own)
+__device__ __forceinline__ float wfrag_elem(const dhaug_wfrag_desc& d, int n, int k) {
+    if (d.W2 == nullptr) return d.W[(long long)n * d.ldw + d.k0 + k];
+    const float* a = d.W + (long long)n * d.ldw;
+    const float* b = d.W2 + d.k0 + k;
+    double s = 0.0;
+    for (int m = 0; m < d.K2; ++m) s = fma((double)a[m], (double)b[(long long)m * d.ldw2], s);
+    return (float)s;
+}
+
+// bias of output feature t: bias[t], or W * bias2 + bias of the composite (same accumulation)
+__device__ __forceinline__ float wfrag_bias(const dhaug_wfrag_desc& d, int t) {
+    double s = d.bias != nullptr ? (double)d.bias[t] : 0.0;
+    if (d.W2 != nullptr && d.bias2 != nullptr) {
+        const float* a = d.W + (long long)t * d.ldw;
+        double c = 0.0;
+        for (int m = 0; m < d.K2; ++m) c = fma((double)a[m], (double)d.bias2[m], c);
+        s += c;
+    }
+    return (float)s;
+}
+
+// one descriptor's fragment blob, zero-padded fp32 bias [256] and, for a logit layer folded into its producer, DOT_OUT vector
+// [257]: the ONE routine behind the batch re-pack and the stand-alone composite pack (a fresh build and an in-place re-pack give
+// the same bits).  Grid: blockIdx.x strides the blob, block 0 also writes the vectors; 256 threads.
+__device__ __forceinline__ void pack_desc(const dhaug_wfrag_desc& d) {
     const long long total = (long long)8 * d.ksteps * 64 * 8;
     uint16_t* dst = static_cast<uint16_t*>(d.dst);
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
@@ -1423,17 +1447,26 @@ __global__ __launch_bounds__(256) void pack_wfrag_batch_kernel(const dhaug_wfrag
         const long long blk = i >> 9;
         const int ks = (int)(blk % d.ksteps), sl = (int)(blk / d.ksteps);
         const int n = 32 * sl + (lane & 31), k = 16 * ks + 8 * (lane >> 5) + j;
-        dst[i] = (n < d.N && k < d.K) ? dhaug_f32_to_bf16(d.W[(long long)n * d.ldw + d.k0 + k]) : (uint16_t)0;
+        dst[i] = (n < d.N && k < d.K) ? dhaug_f32_to_bf16(wfrag_elem(d, n, k)) : (uint16_t)0;
     }
     if (blockIdx.x == 0) {
         const int t = threadIdx.x;
-        if (d.bias_dst != nullptr) d.bias_dst[t] = (d.bias != nullptr && t < d.N) ? d.bias[t] : 0.0f;
+        if (d.bias_dst != nullptr) d.bias_dst[t] = t < d.N ? wfrag_bias(d, t) : 0.0f;
         if (d.dot_dst != nullptr) {                                          // (N == 1: the layer's weights as bf16 values, bias at [256])
-            d.dot_dst[t] = t < d.K ? dhaug_bf16_to_f32(dhaug_f32_to_bf16(d.W[d.k0 + t])) : 0.0f;
-            if (t == 0) d.dot_dst[256] = d.bias != nullptr ? d.bias[0] : 0.0f;
+            d.dot_dst[t] = t < d.K ? dhaug_bf16_to_f32(dhaug_f32_to_bf16(wfrag_elem(d, 0, t))) : 0.0f;
+            if (t == 0) d.dot_dst[256] = wfrag_bias(d, 0);
         }
     }
 }
+
+// every layer of a network in ONE launch (after an optimizer step): blockIdx.y = descriptor
+__global__ __launch_bounds__(256) void pack_wfrag_batch_kernel(const dhaug_wfrag_desc* __restrict__ descs) {
+    const dhaug_wfrag_desc d = descs[blockIdx.y];
+    pack_desc(d);
+}
+
+// one descriptor handed over by value (dhaug_pack_wfrag_composed)
+__global__ __launch_bounds__(256) void pack_wfrag_desc_kernel(const dhaug_wfrag_desc d) { pack_desc(d); }
 
 // how unit i is executed (see the dispatch in fused_mlp_kernel): a run of >= min_run full-width 256 -> 256 layers goes to
 // gemm_stack, together with the narrow layer (K <= 128) feeding it and the <= 64-wide fp32 output layer behind it
@@ -1511,6 +1544,21 @@ int dhaug_pack_wfrag_batch(const dhaug_wfrag_desc* descs_device, int n, void* st
     if (n == 0) return DHAUG_OK;
     DHAUG_CHECK_PTR(descs_device);
     hipLaunchKernelGGL(pack_wfrag_batch_kernel, dim3(64, (unsigned)n), dim3(256), 0, (hipStream_t)stream, descs_device);
+    return dhaug_launch_status();
+}
+
+int dhaug_pack_wfrag_composed(const float* Wa, int64_t ldwa, const float* bias_a, const float* Wb, int64_t ldwb, const float* bias_b,
+                              uint16_t* dst, float* bias_dst, int64_t N, int64_t Ki, int64_t K, int64_t k0, void* stream) {
+    DHAUG_CHECK(N >= 1 && Ki >= 1 && K >= 1 && k0 >= 0 && ldwa >= Ki && ldwb >= k0 + K, DHAUG_EINVAL);
+    DHAUG_CHECK_PTR(Wa); DHAUG_CHECK_PTR(Wb); DHAUG_CHECK_PTR(dst);
+    DHAUG_CHECK(dhaug_aligned16(dst), DHAUG_EALIGN);
+    const int ksteps = (int)((K + 63) / 64) * 4;
+    DHAUG_CHECK(ksteps <= MLP_MAX_KSTEPS && N <= 256 && Ki <= (1 << 20), DHAUG_EUNSUPPORTED);
+    dhaug_wfrag_desc d = {};
+    d.W = Wa; d.ldw = ldwa; d.dst = dst; d.bias = bias_a; d.bias_dst = bias_dst; d.dot_dst = nullptr;
+    d.N = (int32_t)N; d.K = (int32_t)K; d.k0 = (int32_t)k0; d.ksteps = ksteps;
+    d.W2 = Wb; d.bias2 = bias_b; d.ldw2 = ldwb; d.K2 = (int32_t)Ki;
+    hipLaunchKernelGGL(pack_wfrag_desc_kernel, dim3(64), dim3(256), 0, (hipStream_t)stream, d);
     return dhaug_launch_status();
 }
 

@@ -4,7 +4,10 @@ A network is compiled into a short program of units (include/dhaug.h, struct dha
 activation buffers; its weights are re-packed into MFMA fragment order (dhaug_pack_wfrag) whenever a parameter
 changes (the optimizer step invalidates the cache).  Used for the no-grad passes of the hot path: sampling fakes
 (model_fk_gan_train.py:305-308 `.data`), the flipped critic evaluations of the G step (:463-468) and inference.
-Same arithmetic as the layer-by-layer bf16 path (bf16 operands, fp32 accumulate, bf16 activations)."""
+Same arithmetic as the layer-by-layer bf16 path (bf16 operands, fp32 accumulate, bf16 activations), with one difference in
+the 2D critic's bf16 inference program: pose_layer_4 (no activation) and layer_last run as ONE layer whose weights are the
+product of the two fp32 matrices, rounded to bf16 once (dhaug_pack_wfrag_composed) -- where the layered path rounds each
+matrix and the activation between them.  The f16x3 and forward-with-save programs keep every layer."""
 import ctypes
 
 import torch
@@ -29,9 +32,13 @@ def supported(*dims):
 
 
 class _Layer:
-    """packed fragments + padded bias of one nn.Linear (optionally split over two input column ranges)"""
+    """packed fragments + padded bias of one nn.Linear (optionally split over two input column ranges), or of the composite
+    of two: lin = (first, second), two layers with nothing between them -- second(first(x)) as one layer (bf16 mode only)"""
 
     def __init__(self, lin, splits=None, mode="bf16", t16=False):
+        if isinstance(lin, tuple):
+            self._init_composed(lin, splits)
+            return
         W, b = lin.weight.detach(), lin.bias.detach()
         self.t16 = bool(t16) and mode == "f16x3"             # fragments in the order of v_mfma_f32_16x16x32_f16 (DHAUG_MLP_F_T16)
         N, K = W.shape
@@ -59,13 +66,36 @@ class _Layer:
             self.dot[256] = b[0]
         self.lin, self.splits = lin, splits
 
+    def _init_composed(self, lin, splits):
+        first, second = lin
+        Wb, Wa = first.weight.detach(), second.weight.detach()
+        (Ki, K), N = Wb.shape, Wa.shape[0]
+        assert Wa.shape[1] == Ki and first.bias is not None and second.bias is not None
+        self.t16, self.N = False, N
+        splits = splits or [(0, K)]
+        self.w, self.ksteps = [], []
+        self.bias = torch.zeros(256, dtype=torch.float32, device=Wa.device)
+        for i, (k0, k) in enumerate(splits):
+            blob = torch.empty(8 * ((k + 63) // 64 * 4) * 512, dtype=torch.bfloat16, device=Wa.device)
+            _lib.call("dhaug_pack_wfrag_composed", _vp(Wa.data_ptr()), Ki, _vp(second.bias.data_ptr()), _vp(Wb.data_ptr()), K,
+                      _vp(first.bias.data_ptr()), _vp(blob.data_ptr()), _vp(self.bias.data_ptr()) if i == 0 else None, N, Ki, k, k0,
+                      ops._stream())
+            self.w.append(blob)
+            self.ksteps.append((k + 15) // 16)
+        self.zero = torch.zeros(256, dtype=torch.float32, device=Wa.device) if len(splits) > 1 else None
+        self.lin, self.splits = lin, splits
+
     def descs(self):
         """dhaug_wfrag_desc entries that re-pack this layer in place from its (updated) parameters"""
-        W, b = self.lin.weight, self.lin.bias
+        composed = isinstance(self.lin, tuple)
+        first, last = self.lin if composed else (None, self.lin)
+        W, b = last.weight, last.bias
         out = []
         for i, ((k0, k), blob, ks) in enumerate(zip(self.splits, self.w, self.ksteps)):
             d = _lib.WfragDesc()
             d.W, d.ldw, d.dst, d.N, d.K, d.k0, d.ksteps = W.data_ptr(), W.shape[1], blob.data_ptr(), self.N, k, k0, (k + 63) // 64 * 4
+            if composed:                                      # second operand: the layer applied first
+                d.W2, d.bias2, d.ldw2, d.K2 = first.weight.data_ptr(), first.bias.data_ptr(), first.weight.shape[1], W.shape[1]
             d.bias = b.data_ptr()
             d.bias_dst = self.bias.data_ptr() if i == 0 else None
             d.dot_dst = self.dot.data_ptr() if (i == 0 and hasattr(self, "dot")) else None
@@ -174,7 +204,7 @@ class FusedNet:
                 _lib.call("dhaug_pack_wfrag_batch", self.descs_dev.data_ptr(), self.ndescs, ops._stream())
             else:
                 self.layers = {name: _Layer(lin, splits, self.mode, self.build.get("t16", False))
-                               for name, lin, splits in self.build["layers"](self.module)}
+                               for name, lin, splits in self.build["layers"](self.module, self.mode)}
                 if self.mode == "bf16":
                     ds = [d for L in self.layers.values() for d in L.descs()]
                     arr = (_lib.WfragDesc * len(ds))(*ds)
@@ -227,7 +257,7 @@ def _res_blocks(L, units, names, a=0, b=1, act=ACT_RELU):
 
 
 # ---- generator trunk: z (B,128) fp32 -> head (B,35*R) fp32 ------------------------------------------------------
-def _gen_layers(G):
+def _gen_layers(G, mode="bf16"):
     out = [("preprocess.0", G.preprocess[0], None)]
     for b in ("block1", "block2", "block3"):
         blk = getattr(G, b)
@@ -253,7 +283,26 @@ GEN = dict(layers=_gen_layers, program=_gen_program, t16=False)
 
 
 # ---- 2D critic: x (B,32) fp32 -> logit (B,1) ----------------------------------------------------------------------
-def _d2_layers(D):
+# the 2D critic's layers as (name, activation, residual from d1); Fk_2D_Discriminator.forward is this chain
+_D2_CHAIN = (("pose_layer_1", ACT_LRELU, False), ("pose_layer_2", ACT_LRELU, False), ("pose_layer_3", ACT_LRELU, True),
+             ("pose_layer_4", ACT_NONE, False), ("layer_last", ACT_LRELU, False))
+D2_COMPOSED = "pose_layer_4+layer_last"
+
+
+def _composable(act, res, saved):
+    """may a layer be multiplied into the one behind it?  Only if nothing stands between the two linear maps: no activation,
+    no residual added to its output, and nobody else reads (saves) that output"""
+    return act == ACT_NONE and not res and not saved
+
+
+def _d2_layers(D, mode="bf16", compose=True):
+    """compose: pose_layer_4 has no activation and feeds layer_last alone, so the bf16 inference program runs the two as one
+    layer W_last W_4, W_last b_4 + b_last (re-packed with the others whenever a parameter changes): three wide layers
+    instead of four.  f16x3 (1e-4 against the fp32 reference) and forward-with-save (the backward reads d4) keep both."""
+    _, act4, res4 = _D2_CHAIN[3]
+    if compose and mode == "bf16" and _composable(act4, res4, saved=False):
+        return ([(n, getattr(D, n), None) for n in ("pose_layer_1", "pose_layer_2", "pose_layer_3")] +
+                [(D2_COMPOSED, (D.pose_layer_4, D.layer_last), None), ("layer_pred", D.layer_pred, None)])
     return [(n, getattr(D, n), None) for n in ("pose_layer_1", "pose_layer_2", "pose_layer_3", "pose_layer_4",
                                                 "layer_last", "layer_pred")]
 
@@ -265,10 +314,14 @@ def _d2_program(D, L, inputs, M):
     u = [_unit(LOAD_BF16 if x.dtype == torch.bfloat16 else LOAD_F32, dst=1, cols=32, ld=x.stride(0), g=x),
          _gemm(L["pose_layer_1"], 1, 0, ACT_LRELU, s),                 # d1 -> 0
          _gemm(L["pose_layer_2"], 0, 1, ACT_LRELU, s),                 # d2 -> 1
-         _gemm(L["pose_layer_3"], 1, 0, ACT_LRELU, s, res=0),          # d3 = lrelu(L3 d2 + d1) -> 0 (in place)
-         _gemm(L["pose_layer_4"], 0, 1, ACT_NONE),                     # d4 -> 1
-         _gemm(L["layer_last"], 1, 0, ACT_LRELU, s),
-         _gemm(L["layer_pred"], 0, 1, ACT_NONE, out=out)]
+         _gemm(L["pose_layer_3"], 1, 0, ACT_LRELU, s, res=0)]          # d3 = lrelu(L3 d2 + d1) -> 0 (in place)
+    if D2_COMPOSED in L:
+        u += [_gemm(L[D2_COMPOSED], 0, 1, ACT_LRELU, s),               # lrelu(L_last (L4 d3)) -> 1: d4 is never formed
+              _gemm(L["layer_pred"], 1, 0, ACT_NONE, out=out)]
+    else:
+        u += [_gemm(L["pose_layer_4"], 0, 1, ACT_NONE),                # d4 -> 1
+              _gemm(L["layer_last"], 1, 0, ACT_LRELU, s),
+              _gemm(L["layer_pred"], 0, 1, ACT_NONE, out=out)]
     return u, out
 
 
@@ -276,7 +329,7 @@ D2 = dict(layers=_d2_layers, program=_d2_program, t16=True)
 
 
 # ---- 3D critic: pose (B,48) fp32 + KCS (B,32) bf16 -> logit (B,1) ------------------------------------------------
-def _d3_layers(D):
+def _d3_layers(D, mode="bf16"):
     out = [("special_KCS_previous.0", D.special_KCS_previous[0], None), ("previous.0", D.previous[0], None)]
     for b in ("special_KCS_block1", "special_KCS_block2", "special_KCS_block3", "block1", "block2", "block3",
               "merge_block1"):
@@ -366,7 +419,7 @@ def _d3s_program(D, L, inputs, M):
     return u, dict(cat=cat, y=y, h=h, m0=m0, mh=mh, m1=m1, logits=logits)
 
 
-def _d3s_layers(D):
+def _d3s_layers(D, mode="bf16"):
     out = _d3_layers(D)
     return out
 
@@ -389,7 +442,7 @@ def _d2s_program(D, L, inputs, M):
     return u, dict(d=d, logits=logits)
 
 
-D2S = dict(layers=_d2_layers, program=_d2s_program)
+D2S = dict(layers=lambda D, mode="bf16": _d2_layers(D, mode, compose=False), program=_d2s_program)
 
 
 def step_forward_supported(D):

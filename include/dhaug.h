@@ -626,7 +626,11 @@ typedef struct dhaug_mlp_unit {
  * fused programs: R/models_Fk_GAN/model_fk_gan_train.py:177-230 steps the critics every iteration).  Per descriptor: the
  * fragment blob of W[:, k0:k0+K] (ksteps = K padded to multiples of 64, in units of 16; always 8 slices), the zero-padded
  * fp32 bias [256] (bias_dst, optional) and, for a 1-wide logit layer folded into its producer, the DOT_OUT vector [257]
- * (dot_dst, optional).  descs_device: array of n descriptors in device memory. */
+ * (dot_dst, optional).  descs_device: array of n descriptors in device memory.
+ * Second operand (W2 != NULL): the descriptor stands for the composite of two linear layers with nothing between them,
+ * y = W (W2 x + bias2) + bias: W is [N, ldw >= K2], W2 is [K2, ldw2], and (k0, K) selects columns of W2.  The blob holds
+ * bf16( (W W2)[n][k0 + k] ) and bias_dst W bias2 + bias; see dhaug_pack_wfrag_composed for the precision.  W2 == NULL: one
+ * layer, the other three fields are not read. */
 typedef struct dhaug_wfrag_desc {
     const float* W;
     int64_t ldw;
@@ -635,13 +639,29 @@ typedef struct dhaug_wfrag_desc {
     float* bias_dst;
     float* dot_dst;
     int32_t N, K, k0, ksteps;
+    const float* W2;              /* composite: the layer applied FIRST, [K2, ldw2]; NULL: a single layer              */
+    const float* bias2;           /* its bias [K2] (optional)                                                          */
+    int64_t ldw2;
+    int32_t K2;                   /* inner width: output features of W2 = input features of W                          */
+    int32_t pad_;
 } dhaug_wfrag_desc;
 int dhaug_pack_wfrag_batch(const dhaug_wfrag_desc* descs_device, int n, void* stream);
+
+/* Fragment blob (layout of dhaug_pack_wfrag) and zero-padded fp32 bias [256] of the composite of two nn.Linear layers with no
+ * activation, residual or consumer between them: y = Wa (Wb x + bias_b) + bias_a, Wa [N, ldwa >= Ki], Wb [Ki, ldwb >= k0 + K].
+ *   dst      <- bf16( sum_m Wa[n][m] Wb[m][k0 + k] ),   bias_dst[n] <- sum_m Wa[n][m] bias_b[m] + bias_a[n]   (biases optional)
+ * Precision: formed from the fp32 parameters, every sum accumulated in fp64 in the order m = 0 .. Ki-1, rounded to fp32 and then
+ * ONCE to bf16 -- neither factor is rounded to bf16 on its own, and the intermediate activation Wb x + bias_b, which a chain of
+ * two layers rounds to bf16, does not exist.  The same device routine serves a descriptor with W2 set in dhaug_pack_wfrag_batch:
+ * identical bits.  N <= 256, K <= 256. */
+int dhaug_pack_wfrag_composed(const float* Wa, int64_t ldwa, const float* bias_a, const float* Wb, int64_t ldwb, const float* bias_b,
+                              uint16_t* dst, float* bias_dst, int64_t N, int64_t Ki, int64_t K, int64_t k0, void* stream);
 
 /* Runs the program on every 128-row tile of the batch: replaces the nn.Sequential / myResNet stacks of
  * R/models_Fk_GAN/Fk_generator.py:115-119, Fk_discriminator.py:180-201 and :253-266 (inference / sampling passes).
  * bf16 operands, fp32 accumulate, bf16 activations between layers -- the same arithmetic as a chain of
- * dhaug_gemm_bf16 calls. */
+ * dhaug_gemm_bf16 calls over the layers the program holds (a caller may hand over two layers with nothing between them as one:
+ * dhaug_pack_wfrag_composed). */
 int dhaug_mlp_forward(const dhaug_mlp_unit* units, int nunits, int64_t M, void* stream);
 
 /* Parity-grade variant of the same programs: every operand is an fp16 pair x = hi + lo (22 mantissa bits), a product is
