@@ -1019,11 +1019,14 @@ def critic_scalars(logits, pen, B, lam):
 
 def rank1_mask(seed, w_col, mask, n, act, slope=0.0, out=None):
     """bf16 (M, pad): bf16(seed[r] * w[c]) * act'(mask[r][c]) -- the first backward step through a 1-wide logit layer.
-    seed (M, >=1) bf16 (column 0), w_col: bf16 view with the layer's n weights along dim 0 (any stride)"""
+    seed (M, >=1) bf16 (column 0), w_col: bf16 view with the layer's n weights along dim 0 (any stride); mask (M, >= ceil16 n):
+    the kernel writes as many columns as it reads mask columns, and every one of the result's ceil16 n columns is an operand
+    column of the K-padded GEMM behind it"""
     assert seed.dtype == BF16 and w_col.dtype == BF16 and mask.dtype == BF16
-    M, pad = mask.shape[0], min(mask.shape[1], ceil_to(n, 16))
+    M, pad = mask.shape[0], ceil_to(n, 16)
+    assert mask.shape[1] >= pad, "rank1_mask: the mask has %d columns, the result %d" % (mask.shape[1], pad)
     if out is None:
-        out = torch.empty((M, ceil_to(n, 16)), dtype=BF16, device=mask.device)
+        out = torch.empty((M, pad), dtype=BF16, device=mask.device)
     bits = getattr(mask, "_dhaug_bits", None)
     if bits is not None and n == 256 and act != 0 and out.stride(0) % 8 == 0 and out.shape[1] >= 256:
         assert bits.device == out.device, "sign bits must live on the operands' device"

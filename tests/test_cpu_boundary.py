@@ -199,6 +199,187 @@ def test_pose_and_elem_argument_errors(built):
         assert L.dhaug_center_flip(None, None, 0, C, 1, 1, None) == EINVAL                                    # (checked before the empty batch)
 
 
+def test_stream_elem_argument_errors(built):
+    """the packing, column-sum, activation-backward, rank-one and Adam entry points of csrc/dhaug_elem.hip (the table of
+    tests/test_gpu_stream_elem.py): every DHAUG_CHECK returns its documented code before any launch -- all pointers are HOST
+    addresses, so a call that reached a launch would return a HIP error instead -- and an empty batch looks at no pointer"""
+    import dhaug_amd
+    L = dhaug_amd._lib.lib()
+    buf = (ctypes.c_float * 8192)()
+    base = (ctypes.addressof(buf) + 15) & ~15
+    a, b, c, d = (ctypes.c_void_p(base + 4096 * i) for i in range(4))
+    mis2, mis8 = ctypes.c_void_p(base + 2), ctypes.c_void_p(base + 8)
+    EINVAL, EALIGN, EUNSUPPORTED = -1, -2, -3
+    # cast_pad: (src, ld_src, dst, ld_dst, rows, cols, pad_cols)
+    for args in ((a, 30, b, 32, -1, 30, 32), (a, 30, b, 32, 4, 0, 32), (a, 30, b, 32, 4, 30, 28), (a, 29, b, 32, 4, 30, 32),
+                 (a, 30, b, 30, 4, 30, 32), (None, 30, b, 32, 4, 30, 32), (a, 30, None, 32, 4, 30, 32)):
+        assert L.dhaug_cast_pad_bf16(*args, None) == EINVAL, args
+    for args in ((a, 30, b, 32, 4, 30, 31), (a, 30, b, 33, 4, 30, 32), (a, 30, mis2, 32, 4, 30, 32)):      # odd pad_cols / ld_dst, dst % 4
+        assert L.dhaug_cast_pad_bf16(*args, None) == EALIGN, args
+    assert L.dhaug_cast_pad_bf16(None, 30, None, 32, 0, 30, 32, None) == 0
+    # cast_transpose: rows >= 1 (no empty batch), pad_cols >= rows
+    for args in ((a, 30, b, 16, 0, 30, 16), (a, 30, b, 16, 4, 0, 16), (a, 30, b, 16, 20, 30, 16), (a, 29, b, 16, 4, 30, 16),
+                 (a, 30, b, 8, 4, 30, 16), (None, 30, b, 16, 4, 30, 16), (a, 30, None, 16, 4, 30, 16)):
+        assert L.dhaug_cast_transpose_bf16(*args, None) == EINVAL, args
+    # split_bf16: (src, ld_src, dst, rows, cols, pad_cols, mode, terms); split_f16: (..., mode)
+    for args in ((a, 30, b, -1, 30, 32, 0, 3), (a, 30, b, 4, 0, 32, 0, 3), (a, 30, b, 4, 30, 24, 0, 3), (a, 29, b, 4, 30, 32, 0, 3),
+                 (a, 30, b, 4, 30, 32, 3, 6), (a, 30, b, 4, 30, 32, -1, 6), (a, 30, b, 4, 30, 32, 2, 3), (a, 30, b, 4, 30, 32, 0, 4),
+                 (None, 30, b, 4, 30, 32, 0, 3), (a, 30, None, 4, 30, 32, 0, 3)):
+        assert L.dhaug_split_bf16(*args, None) == EINVAL, args
+    for args in ((a, 30, b, 4, 30, 36, 0, 3), (a, 30, mis8, 4, 30, 32, 0, 3)):                             # pad_cols % 8, dst % 16
+        assert L.dhaug_split_bf16(*args, None) == EALIGN, args
+    assert L.dhaug_split_bf16(None, 30, None, 0, 30, 32, 0, 3, None) == 0
+    for args in ((a, 30, b, -1, 30, 32, 0), (a, 30, b, 4, 0, 32, 0), (a, 30, b, 4, 30, 24, 0), (a, 29, b, 4, 30, 32, 0),
+                 (a, 30, b, 4, 30, 32, 3), (None, 30, b, 4, 30, 32, 0), (a, 30, None, 4, 30, 32, 0)):
+        assert L.dhaug_split_f16(*args, None) == EINVAL, args
+    for args in ((a, 30, b, 4, 30, 36, 0), (a, 30, mis8, 4, 30, 32, 0)):
+        assert L.dhaug_split_f16(*args, None) == EALIGN, args
+    assert L.dhaug_split_f16(None, 30, None, 0, 30, 32, 2, None) == 0
+    # repack_weights / adam_repack_step: counts in range, no null where something is to do
+    assert L.dhaug_repack_weights(a, -1, None) == EINVAL and L.dhaug_repack_weights(a, 65536, None) == EINVAL
+    assert L.dhaug_repack_weights(None, 3, None) == EINVAL and L.dhaug_repack_weights(None, 0, None) == 0
+    rs = lambda p=a, st=b, descs=c, ndesc=2, nitems=5, w=d, nw=1: L.dhaug_adam_repack_step(p, a, a, a, 1e-4, 0.5, 0.9, 1e-8, st, 1.0, descs, ndesc,
+                                                                                           nitems, w, nw, None)
+    assert rs(ndesc=-1) == EINVAL and rs(nitems=-1) == EINVAL and rs(nw=-1) == EINVAL and rs(nw=65536) == EINVAL
+    assert rs(st=None) == EINVAL and rs(p=None) == EINVAL and rs(descs=None) == EINVAL
+    # column sums: (src, ld, dst, M, N, accumulate).  (M = 0 without accumulate clears dst on the device: tests/test_gpu_stream_elem.py)
+    for fn in (L.dhaug_colsum_f32, L.dhaug_colsum_bf16):
+        for args in ((a, 8, b, -1, 8, 1), (a, 8, b, 4, 0, 1), (a, 7, b, 4, 8, 1), (a, 8, None, 4, 8, 1), (None, 8, b, 4, 8, 1)):
+            assert fn(*args, None) == EINVAL, args
+        assert fn(None, 8, b, 0, 8, 1, None) == 0
+    # act_backward_bf16: (g, ld_g, y, ld_y, dst, ld_dst, M, N, act, slope)
+    for args in ((a, 16, b, 16, c, 16, -1, 16, 1, 0.0), (a, 16, b, 16, c, 16, 4, 0, 1, 0.0), (a, 16, b, 16, c, 16, 4, 7, 1, 0.0),
+                 (a, 16, b, 16, c, 16, 4, 16, 3, 0.0), (a, 16, b, 16, c, 16, 4, 16, -1, 0.0), (None, 16, b, 16, c, 16, 4, 16, 1, 0.0),
+                 (a, 16, None, 16, c, 16, 4, 16, 1, 0.0), (a, 16, b, 16, None, 16, 4, 16, 1, 0.0)):
+        assert L.dhaug_act_backward_bf16(*args, None) == EINVAL, args
+    for args in ((a, 16, b, 16, c, 16, 4, 12, 1, 0.0), (a, 20, b, 16, c, 16, 4, 16, 1, 0.0), (a, 16, b, 20, c, 16, 4, 16, 1, 0.0),
+                 (a, 16, b, 16, c, 20, 4, 16, 1, 0.0), (mis2, 16, b, 16, c, 16, 4, 16, 1, 0.0), (a, 16, mis8, 16, c, 16, 4, 16, 1, 0.0),
+                 (a, 16, b, 16, mis8, 16, 4, 16, 1, 0.0)):
+        assert L.dhaug_act_backward_bf16(*args, None) == EALIGN, args
+    assert L.dhaug_act_backward_bf16(None, 16, None, 16, None, 16, 0, 16, 1, 0.0, None) == 0
+    for args in ((a, b, c, -1, 1, 0.0), (a, b, c, 4, 3, 0.0), (a, b, c, 4, -1, 0.0), (None, b, c, 4, 1, 0.0), (a, None, c, 4, 1, 0.0),
+                 (a, b, None, 4, 1, 0.0)):
+        assert L.dhaug_act_backward_f32(*args, None) == EINVAL, args
+    assert L.dhaug_act_backward_f32(None, None, None, 0, 2, 0.1, None) == 0
+    for args in ((a, b, c, -1), (None, b, c, 4), (a, None, c, 4), (a, b, None, 4)):
+        assert L.dhaug_add_f32(*args, None) == EINVAL, args
+    assert L.dhaug_add_f32(None, None, None, 0, None) == 0
+    # Adam: (p, g, m, v, n, lr, b1, b2, eps, step | step_dev, grad_scale); step >= 1
+    hp = (1e-4, 0.5, 0.9, 1e-8)
+    for ptrs, n, step in (((a, b, c, d), -1, 1), ((a, b, c, d), 4, 0), ((a, b, c, d), 4, -3), ((a, b, c, d), 0, 0), ((None, b, c, d), 4, 1),
+                          ((a, None, c, d), 4, 1), ((a, b, None, d), 4, 1), ((a, b, c, None), 4, 1)):
+        assert L.dhaug_adam_step(*ptrs, n, *hp, step, 1.0, None) == EINVAL, (n, step)
+    assert L.dhaug_adam_step(None, None, None, None, 0, *hp, 1, 1.0, None) == 0
+    for ptrs, n, cnt in (((a, b, c, d), -1, a), ((None, b, c, d), 4, a), ((a, None, c, d), 4, a), ((a, b, None, d), 4, a),
+                         ((a, b, c, None), 4, a), ((a, b, c, d), 4, None)):
+        assert L.dhaug_adam_step_dev(*ptrs, n, *hp, cnt, 1.0, None) == EINVAL, n
+    assert L.dhaug_adam_step_dev(None, None, None, None, 0, *hp, None, 1.0, None) == 0
+    assert L.dhaug_counter_add(None, 1, None) == EINVAL
+    # rank1_mask: (seed, ld_seed, w, ld_w, mask, ld_mask, out, ld_out, M, N, pad_cols, mask_act, mask_slope)
+    for args in ((a, 1, b, 1, c, 112, d, 112, -1, 100, 112, 1, 0.0), (a, 1, b, 1, c, 112, d, 112, 4, 0, 112, 1, 0.0),
+                 (a, 1, b, 1, c, 112, d, 112, 4, 100, 96, 1, 0.0), (a, 1, b, 1, c, 112, d, 112, 4, 100, 100, 1, 0.0),
+                 (a, 1, b, 1, c, 112, d, 112, 4, 100, 112, 0, 0.0), (a, 1, b, 1, c, 112, d, 112, 4, 100, 112, 3, 0.0),
+                 (None, 1, b, 1, c, 112, d, 112, 4, 100, 112, 1, 0.0), (a, 1, None, 1, c, 112, d, 112, 4, 100, 112, 1, 0.0),
+                 (a, 1, b, 1, None, 112, d, 112, 4, 100, 112, 1, 0.0), (a, 1, b, 1, c, 112, None, 112, 4, 100, 112, 1, 0.0)):
+        assert L.dhaug_rank1_mask_bf16(*args, None) == EINVAL, args
+    assert L.dhaug_rank1_mask_bf16(a, 1, b, 1, c, 1032, d, 1032, 4, 1025, 1032, 1, 0.0, None) == EUNSUPPORTED     # pad_cols > 1 024
+    for args in ((a, 0, b, 1, c, 112, d, 112, 4, 100, 112, 1, 0.0), (a, 1, b, 0, c, 112, d, 112, 4, 100, 112, 1, 0.0),
+                 (a, 1, b, 1, c, 104, d, 112, 4, 100, 112, 1, 0.0), (a, 1, b, 1, c, 112, d, 104, 4, 100, 112, 1, 0.0),
+                 (a, 1, b, 1, c, 116, d, 112, 4, 100, 112, 1, 0.0), (a, 1, b, 1, c, 112, d, 116, 4, 100, 112, 1, 0.0),
+                 (a, 1, b, 1, mis8, 112, d, 112, 4, 100, 112, 1, 0.0), (a, 1, b, 1, c, 112, mis8, 112, 4, 100, 112, 1, 0.0)):
+        assert L.dhaug_rank1_mask_bf16(*args, None) == EALIGN, args
+    assert L.dhaug_rank1_mask_bf16(None, 1, None, 1, None, 112, None, 112, 0, 100, 112, 1, 0.0, None) == 0
+    # rank1_bits: (seed, ld_seed, w, ld_w, bits, out, ld_out, M, mask_act, mask_slope)
+    for args in ((a, 1, b, 1, c, d, 256, -1, 1, 0.0), (a, 1, b, 1, c, d, 256, 4, 0, 0.0), (None, 1, b, 1, c, d, 256, 4, 1, 0.0),
+                 (a, 1, None, 1, c, d, 256, 4, 1, 0.0), (a, 1, b, 1, None, d, 256, 4, 1, 0.0), (a, 1, b, 1, c, None, 256, 4, 1, 0.0)):
+        assert L.dhaug_rank1_bits_bf16(*args, None) == EINVAL, args
+    for args in ((a, 0, b, 1, c, d, 256, 4, 1, 0.0), (a, 1, b, 0, c, d, 256, 4, 1, 0.0), (a, 1, b, 1, c, d, 248, 4, 1, 0.0),
+                 (a, 1, b, 1, c, d, 260, 4, 1, 0.0), (a, 1, b, 1, mis8, d, 256, 4, 1, 0.0), (a, 1, b, 1, c, mis8, 256, 4, 1, 0.0)):
+        assert L.dhaug_rank1_bits_bf16(*args, None) == EALIGN, args
+    assert L.dhaug_rank1_bits_bf16(None, 1, None, 1, None, None, 256, 0, 2, 0.2, None) == 0
+
+
+def test_stream_elem_references_reject_emulated_faults():
+    """tests/stream_elem_util.py on the host, at small sizes: its references accept a faithful emulation of each kernel's output and
+    the comparisons of tests/test_gpu_stream_elem.py reject the faults a streaming kernel can have -- the last row dropped, the tail
+    chunk of a row left unwritten, one element written past the pad, the second trip of a capped loop skipped (out of place, in
+    place, and in Adam), the column-sum fold pairing r with r + 1"""
+    import stream_elem_util as S
+    BF16 = torch.bfloat16
+    payload = S.bf16_from_bits([S.PAYLOAD16])[0]
+
+    def emulate(ref, ld):
+        """a payload-filled (rows, ld) output that a faithful kernel wrote ref into"""
+        out = payload.repeat(ref.shape[0], ld)
+        out[:, :ref.shape[1]] = ref
+        return out
+
+    x = S.special_matrix(9, 30, S.SPECIAL_F32, seed=1)
+    cases = [("cast_pad", S.cast_pad_ref(x, 32)), ("cast_transpose", S.cast_transpose_ref(x, 16)),
+             ("split_bf16 (1, 6)", S.split_ref(x, S.SPLIT_BF16_LAYOUT[(1, 6)], 32, False)),
+             ("split_f16 2", S.split_ref(S.special_matrix(9, 30, S.SPECIAL_F16_SAFE, seed=2), S.SPLIT_F16_LAYOUT[2], 32, True))]
+    g = S.gen(3)
+    gv, yv = torch.randn(9, 32, generator=g).to(BF16), S.plant_mask(torch.randn(9, 32, generator=g).to(BF16), seed=4)
+    cases.append(("act_backward", S.act_backward_ref(gv, yv, 2, 0.01)))
+    sd, w = torch.randn(9, generator=g).to(BF16), torch.randn(30, generator=g).to(BF16)
+    cases.append(("rank1", S.rank1_ref(sd, w, yv, 30, 32, 0.2)))
+    for name, ref in cases:
+        ref = ref.view(BF16) if ref.dtype != BF16 else ref                # (16-bit patterns: the comparison is on bits)
+        width = ref.shape[1]
+        good = emulate(ref, width + 8)
+        assert S.rows_ok(good, width, ref, nan_ok=True), name
+        bad = good.clone(); bad[-1] = payload                             # the last row dropped
+        assert not S.rows_ok(bad, width, ref, nan_ok=True), name
+        bad = good.clone(); bad[:, width - 8:width] = payload             # the tail chunk of every row left unwritten
+        assert not S.rows_ok(bad, width, ref, nan_ok=True), name
+        bad = good.clone(); bad[-1, width - 8:width] = payload            # ... of the last row only
+        assert not S.rows_ok(bad, width, ref, nan_ok=True), name
+        bad = good.clone(); bad[4, width] = 0.0                           # one element past the pad written (a zero, as a pad would be)
+        assert not S.rows_ok(bad, width, ref, nan_ok=True), name
+        flat = good.clone()                                               # the second trip skipped: items beyond the first 2/3 untouched
+        flat[6:] = payload
+        assert not S.rows_ok(flat, width, ref, nan_ok=True), name
+    # a pad column that holds data instead of zeros, a duplicated segment that differs
+    ref = S.split_ref(x, S.SPLIT_BF16_LAYOUT[(0, 3)], 32, False)
+    bad = ref.clone(); bad[:, 31] = bad[:, 29]
+    assert not S.rows_ok(bad, 96, ref) and S.rows_ok(ref.clone(), 96, ref, nan_ok=True)
+    # in place, the second trip skipped: the skipped rows still hold g, which differs from g * act'(y) wherever y <= 0
+    for act in (1, 2):
+        ref = S.act_backward_ref(gv, yv, act, 0.01)
+        stale = ref.clone(); stale[6:] = gv[6:]
+        assert S.rows_ok(ref.clone(), 32, ref) and not S.rows_ok(stale, 32, ref), act
+    # the bit compare of rank1_mask against the float compare: a signed 16-bit compare would differ only on NaN masks; a compare that
+    # took -0 or a negative subnormal for positive is rejected by the planted values
+    wrong = torch.where(S.ibits(yv) != 0, gv.float(), gv.float() * 0.01).to(BF16)
+    assert not S.rows_ok(wrong, 32, S.act_backward_ref(gv, yv, 2, 0.01))
+    # column sums: a dropped row; the fold
+    xi = S.int_matrix(65, 9, seed=5)
+    assert S.exact_sums_ok(xi.sum(0), xi) and not S.exact_sums_ok(xi[:-1].sum(0), xi)
+    y = S.folded(torch.randn(72, 64, generator=S.gen(6)))
+    assert float(S.colsum_emulate(y, lambda r, h: r + h).abs().max()) == 0.0               # the kernel's pairing: exactly zero
+    assert float(S.colsum_emulate(y, lambda r, h: r + 1).abs().max()) > 0.0                # r with r + 1: it is not
+    # Adam at two small sizes: the fp32 restatement passes its own rule; one skipped element, a skipped tail and a missing
+    # grad_scale do not; the multi-pass size and its bounds are checked here too (the condition bound(p) < lr / 10)
+    for n in (257, 1000):
+        c = S.adam_case(n)
+        assert S.adam_check("ref32 n=%d" % n, c["ref32"], c)[0] < S.ADAM_LR / 10
+        one = c["ref32"][0].clone(); one[n // 2] = c["p0"][n // 2]
+        tail = c["ref32"][0].clone(); tail[256:] = c["p0"][256:]
+        for bad in (one, tail):
+            with pytest.raises(AssertionError):
+                S.adam_check("faulty", (bad, c["ref32"][1], c["ref32"][2]), c)
+        p, m, v = c["p0"], torch.zeros(n), torch.zeros(n)
+        for step, gr in zip(S.ADAM_STEPS, c["grads"]):
+            p, m, v = S.adam_ref(p, gr, m, v, step, torch.float32, gscale=1.0)
+        with pytest.raises(AssertionError):
+            S.adam_check("no grad_scale", (p, m, v), c)
+        z = S.ADAM_ZERO_AT
+        assert S.ibits(c["ref32"][0])[z] == S.ibits(c["p0"])[z]                              # g = m = v = 0 keeps the parameter's bits
+    for kernel in ("cast_pad", "cast_transpose", "split", "act_bf16", "rank1", "flat", "adam_nt"):
+        n, per = S.items(kernel)
+        assert per < n < 2 * per, kernel                                                    # exactly one more, partial, trip
+
+
 def test_parity_program_planner_refuses_what_one_image_cannot_hold(built):
     """dhaug_mlp_forward_x3 plans the three virtual buffers of a program onto ONE in-place LDS image (+ registers + a workspace)
     on the host, before any launch: a program that reads a value from where it no longer is comes back DHAUG_EUNSUPPORTED, mixed
