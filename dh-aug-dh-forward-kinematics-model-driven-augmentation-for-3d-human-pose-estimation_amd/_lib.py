@@ -84,6 +84,9 @@ SIGNATURES = {
     "dhaug_bn_act_backward": [_vp, _i32, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _f32, _u64, _u64, _vp, _vp, _i64, _vp, _i64, _vp,
                               _vp, _i64, _i64, _vp],
     "dhaug_bn_fold": [_vp, _i64, _vp, _vp, _vp, _vp, _f32, _vp, _i64, _vp, _vp, _i64, _i64, _vp],
+    "dhaug_conv_taps_pack_bf16": [_vp, _i64, _i64, _i32, _vp, _i64, _vp, _i64, _vp],
+    "dhaug_conv_taps_permute_f32": [_vp, _vp, _i64, _i64, _i32, _i32, _i32, _vp],
+    "dhaug_tap_gather": [_vp, _i32, _i64, _i64, _i64, _i64, _i32, _i32, _i32, _vp, _i64, _vp, _i64, _vp],
 }
 BN_MAX_CHUNKS = 32                                     # DHAUG_BN_MAX_CHUNKS of include/dhaug.h
 

@@ -27,6 +27,13 @@ from . import ops
 BF16 = torch.bfloat16
 ACT_NONE, ACT_RELU, ACT_LRELU = 0, 1, 2
 TERMS = {"bf16x3": 3, "bf16x6": 6}
+# 'bf16x6' with the five correction segments of an NT product accumulated FIRST and the hi * hi segment last (_nt_split): the
+# multi-frame posenets' parity arithmetic.  In one launch over K' = 6 K the accumulator reaches its full size after the first sixth
+# of the steps, and every later step, which adds a term 2^-9 of that size or smaller, still rounds at 2^-24 of the FULL accumulator:
+# five sixths of the rounding steps buy nothing (measured on an MI355X against fp64, M = 8, K = 1 024: 1.4e-6 of the largest element,
+# a fp32 GEMM 3.7e-7).  Same operands, same kernel, two launches.
+ORDERED6 = "bf16x6o"
+TERMS[ORDERED6] = 6
 F16X3_LAYER = "f16x3l"     # forward-only layer arithmetic: IEEE-half pairs on dhaug_gemm_f16x3 (see _raw_linear)
 F16X3_PLANES = os.environ.get("DHAUG_F16X3_PLANES", "1") != "0"     # ... with the operand split written by the producing layer's epilogue
 
@@ -201,8 +208,17 @@ def _raw_linear(x, W, bias, res, act, slope, prec, out_f32, out=None):
         prec = "bf16x6"
     T = TERMS[prec]
     x3 = ops.split_bf16(x.float() if x.dtype == BF16 else x, 0, T, Kp)
-    _, cf = ops.gemm_nt(x3, _w_nt(W, Kp, prec), N, T * Kp, bias=bias, res_f32=res, act=act, slope=slope, out_f32=True)
-    return cf
+    return _nt_split(x3, _w_nt(W, Kp, prec), N, Kp, prec, bias, res, act, slope)
+
+
+def _nt_split(a3, b3, N, Kp, prec, bias=None, res=None, act=ACT_NONE, slope=0.0):
+    """fp32 act(a b^T + bias + res) of two split operands (M, T Kp) / (N, T Kp) on gemm_nt; ORDERED6: the segments behind the first
+    (hi * mid, mid * hi, mid * mid, hi * lo, lo * hi) in one launch, then hi * hi with that sum as the epilogue's residual"""
+    T = TERMS[prec]
+    if prec != ORDERED6:
+        return ops.gemm_nt(a3, b3, N, T * Kp, bias=bias, res_f32=res, act=act, slope=slope, out_f32=True)[1]
+    small = ops.gemm_nt(a3[:, Kp:], b3[:, Kp:], N, (T - 1) * Kp, res_f32=res, out_f32=True)[1]
+    return ops.gemm_nt(a3, b3, N, Kp, bias=bias, res_f32=small, act=act, slope=slope, out_f32=True)[1]
 
 
 def _raw_linear_t(g, W, prec, out_f32):
@@ -214,8 +230,7 @@ def _raw_linear_t(g, W, prec, out_f32):
         return cf if out_f32 else cb
     T = TERMS[prec]
     g3 = ops.split_bf16(g, 0, T, Np)
-    _, cf = ops.gemm_nt(g3, _w_nn(W, prec), K, T * Np, out_f32=True)
-    return cf
+    return _nt_split(g3, _w_nn(W, prec), K, Np, prec)
 
 
 def _raw_outer(g, x, N, K, prec, colsum=None, out=None, split=None):
@@ -653,3 +668,101 @@ class BnActFn(torch.autograd.Function):
 def bn_act(z, gamma, beta, residual=None, bn_buffers=None, momentum=0.1, eps=1e-5, p=0.0):
     """the arithmetic follows z's type: bf16 in the 'bf16' mode, fp32 in the split modes"""
     return BnActFn.apply(z, gamma, beta, residual, bn_buffers, momentum, eps, p)
+
+
+# ---------------------------------------------------------------------------------------------------
+# multi-frame posenets: a k-tap Conv1d with stride k over non-overlapping frames, activations as rows (batch-major, then time):
+#     x_rows.view(M / k, k C) @ W2d^T,   W2d[n, j C + c] = W[n, c, j]
+# The tap-major operands are packed from the Conv1d weight where it lies (dhaug_conv_taps_pack_bf16; in the split precisions
+# dhaug_conv_taps_permute_f32 + split_bf16) and cached on the parameter under pack_key like every other weight; the products are the
+# dense layers' (gemm_nt, _raw_outer), and the weight gradient, which the TN product delivers tap-major, is put back into the
+# Conv1d layout by dhaug_conv_taps_permute_f32.
+# ---------------------------------------------------------------------------------------------------
+def _taps_w2d(Wc):
+    N, Cin, k = Wc.shape
+    return ops.conv_taps_permute_f32(Wc.detach(), N, Cin, k, True)
+
+
+def _taps_nt(Wc, prec):
+    """B operand of x W2d^T: (N, k Cin) bf16, or the weight-side split (N, terms * k Cin)"""
+    ent = _pack(Wc)
+    key = ("taps", prec)
+    if prec == "bf16":
+        if key not in ent.nt:
+            ent.nt[key], ent.nn = ops.conv_taps_pack_bf16(Wc.detach())
+        return ent.nt[key]
+    if key not in ent.nt3:
+        ent.nt3[key] = ops.split_bf16(_taps_w2d(Wc), 1, TERMS[prec], Wc.shape[1] * Wc.shape[2])
+    return ent.nt3[key]
+
+
+def _taps_nn(Wc, prec):
+    """B operand of g W2d: (k Cin, ceil16 N) bf16, or the weight-side split of W2d^T"""
+    ent = _pack(Wc)
+    if prec == "bf16":
+        _taps_nt(Wc, prec)
+        return ent.nn
+    if ent.nn3 is None:
+        ent.nn3 = {}
+    key = ("taps", prec)
+    if key not in ent.nn3:
+        ent.nn3[key] = ops.split_bf16(_taps_w2d(Wc).t().contiguous(), 1, TERMS[prec])
+    return ent.nn3[key]
+
+
+def _raw_conv_taps(x2, Wc, prec, out_f32):
+    N, K = Wc.shape[0], Wc.shape[1] * Wc.shape[2]
+    if prec == "bf16":
+        cb, cf = ops.gemm_nt(_operand(x2, K), _taps_nt(Wc, prec), N, K, out_bf16=not out_f32, n_pad=ceil16(N), out_f32=out_f32)
+        return cf if out_f32 else cb
+    T = TERMS[prec]
+    x3 = ops.split_bf16(x2.float() if x2.dtype == BF16 else x2, 0, T, K)
+    return _nt_split(x3, _taps_nt(Wc, prec), N, K, prec)
+
+
+def _raw_conv_taps_t(g, Wc, prec, out_f32):
+    N, K = Wc.shape[0], Wc.shape[1] * Wc.shape[2]
+    Np = ceil16(N)
+    if prec == "bf16":
+        cb, cf = ops.gemm_nt(_operand(g, Np), _taps_nn(Wc, prec), K, Np, out_bf16=not out_f32, n_pad=K, out_f32=out_f32)
+        return cf if out_f32 else cb
+    T = TERMS[prec]
+    return _nt_split(ops.split_bf16(g, 0, T, Np), _taps_nn(Wc, prec), K, Np, prec)
+
+
+class ConvTapsFn(torch.autograd.Function):
+    """y (M / k, N) = x2 W2d^T for x2 (M / k, k Cin), the (M, Cin) rows viewed k at a time: fp32, or bf16 hidden activations.  First
+    order only.  The weight gradient comes back in the Conv1d layout (N, Cin, k), for conv.weight itself."""
+
+    @staticmethod
+    def forward(ctx, x2, Wc, prec, out_f32):
+        ctx.save_for_backward(x2, Wc)
+        ctx.prec = prec
+        return _raw_conv_taps(x2, Wc, prec, out_f32 or prec != "bf16")
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gy):
+        x2, Wc = ctx.saved_tensors
+        prec = ctx.prec
+        N, Cin, k = Wc.shape
+        gz = gy.contiguous()
+        gx = gW = None
+        if ctx.needs_input_grad[0]:
+            gx = _raw_conv_taps_t(gz, Wc, prec, x2.dtype != BF16)
+        if ctx.needs_input_grad[1]:
+            gW = ops.conv_taps_permute_f32(_raw_outer(gz, x2, N, k * Cin, prec), N, Cin, k, False)
+        return gx, gW, None, None
+
+
+def conv_taps(x_rows, conv_weight, k, prec="bf16", out_f32=False):
+    """the k-tap, stride-k Conv1d `conv_weight` (N, Cin, k) over x_rows (M, Cin) (fp32, or bf16 in the 'bf16' mode): (M / k, N), bf16
+    (ceil16 N columns) in the 'bf16' mode unless out_f32, fp32 otherwise"""
+    M, C = x_rows.shape
+    N, Cin, kw = conv_weight.shape
+    if kw != k or Cin != C or M % k or C % 16:
+        raise ValueError("conv_taps: rows %s do not fit a %d-tap convolution with weight %s (the row count must be a multiple of the "
+                         "taps, the channels a multiple of 16)" % (tuple(x_rows.shape), k, tuple(conv_weight.shape)))
+    if not x_rows.is_contiguous():
+        x_rows = x_rows.contiguous()
+    return ConvTapsFn.apply(x_rows.view(M // k, k * C), conv_weight, prec, out_f32)

@@ -28,3 +28,33 @@ def model_pos_preparation(args, dataset, device, flag='train'):
     # else: torch's default initialisation stays.  (The reference applies its init_weights here, which touches nn.Linear modules
     # only; this model holds nn.Conv1d and nn.BatchNorm1d modules and no nn.Linear, so it is a no-op there as well.)
     return model_pos
+
+
+MULTI_FRAME_POSENETS = ("mulit_farme_videopose",)
+
+
+def multi_frame_model_pos_preparation(args, dataset, device, flag='train'):
+    """the reference's `mulit_farme_videopose` branch (R/function_baseline/model_pos_preparation.py:42-50): posenet
+    (B, T, 16, 2) -> (B, T', 16, 3) with filter widths args.architecture ('3,3', '3,3,3', ...); flag 'train' builds the strided
+    multiFrame_TemporalModelOptimized1f, 'test' the dilated multiFrame_TemporalModel.  A factory of its own: model_pos_preparation
+    above keeps refusing every name but `videopose`."""
+    from ..models_Fk_GAN.mulit_farme_videopose import multiFrame_TemporalModel, multiFrame_TemporalModelOptimized1f
+    name = args.posenet_name
+    if name not in MULTI_FRAME_POSENETS:
+        raise NotImplementedError("posenet_name %r is not a multi-frame posenet of this package; implemented: %s"
+                                  % (name, ", ".join(MULTI_FRAME_POSENETS)))
+    if flag not in ("train", "test"):
+        raise ValueError("flag must be 'train' or 'test', got %r" % (flag,))
+    widths = [int(w) for w in str(args.architecture).split(',')]
+    cls = multiFrame_TemporalModelOptimized1f if flag == "train" else multiFrame_TemporalModel
+    model_pos = cls(16, 2, 16, filter_widths=widths, causal=False, dropout=0.25, channels=1024).to(device)
+    count = sum(p.numel() for p in model_pos.parameters())
+    print("posenet %s (%s): filter widths %s, receptive field %d, %d parameters (%.2f M), precision %s"
+          % (name, cls.__name__, widths, model_pos.receptive_field(), count, count / 1e6, model_pos.precision))
+    if getattr(args, "pretrain", False):
+        path = getattr(args, "posenet_pretrain_path", None)
+        if not path:
+            raise ValueError("args.pretrain is set: give the checkpoint as args.posenet_pretrain_path")
+        model_pos.load_state_dict(torch.load(path, map_location=device)['model_pos'])
+        print("posenet %s: weights loaded from %s" % (name, path))
+    return model_pos

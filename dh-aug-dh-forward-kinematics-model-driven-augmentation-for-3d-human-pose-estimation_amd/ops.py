@@ -1243,3 +1243,63 @@ def bn_fold(W, gamma, beta, running_mean, running_var, eps=1e-5, want_weight=Tru
     _lib.call("dhaug_bn_fold", _p(Wd), K, _p(v[0]), _p(v[1]), _p(v[2]), _p(v[3]), float(eps), _p(Wo), K, _p(bias), _p(rstd), N, K,
               _stream())
     return Wo, bias, rstd
+
+
+# ---------------------------------------------------------------------------------------------- multi-frame posenets: tap layout
+def conv_taps_pack_bf16(W, want_nn=True, nt=None, nn=None):
+    """fp32 Conv1d weight (N, Cin, k) -> (nt bf16 (N, k Cin), nn bf16 (k Cin, ceil16 N) | None): dhaug_conv_taps_pack_bf16.
+    nt / nn: write into these (row-strided views allowed) instead of allocating."""
+    w = _dev(W, torch.float32, "conv_taps_pack_bf16")
+    if w.dim() != 3:
+        raise ValueError("conv_taps_pack_bf16: a Conv1d weight (N, Cin, k) is expected, got %s" % (tuple(w.shape),))
+    N, Cin, k = w.shape
+    if nt is None:
+        nt = torch.empty((N, k * Cin), dtype=BF16, device=w.device)
+    if nn is None and want_nn:
+        nn = torch.empty((k * Cin, ceil_to(N, 16)), dtype=BF16, device=w.device)
+    for t, rows in ((nt, N), (nn, k * Cin)):
+        assert t is None or (t.dtype == BF16 and t.is_cuda and t.dim() == 2 and t.stride(1) == 1 and t.shape[0] == rows)
+    _lib.call("dhaug_conv_taps_pack_bf16", _p(w), N, Cin, k, _p(nt), nt.stride(0), _p(nn), 0 if nn is None else nn.stride(0), _stream())
+    return nt, nn
+
+
+def conv_taps_permute_f32(src, N, Cin, k, to_taps, out=None, accumulate=False):
+    """to_taps: fp32 (N, Cin, k) -> (N, k Cin) with out[n, j Cin + c] = src[n, c, j]; otherwise (N, k Cin) -> (N, Cin, k), added
+    into `out` when accumulate is set (dhaug_conv_taps_permute_f32)"""
+    s = _dev(src, torch.float32, "conv_taps_permute_f32")
+    if s.numel() != N * Cin * k:
+        raise ValueError("conv_taps_permute_f32: %d elements given for N, Cin, k = %d, %d, %d" % (s.numel(), N, Cin, k))
+    shape = (N, k * Cin) if to_taps else (N, Cin, k)
+    if out is None:
+        if accumulate:
+            raise ValueError("conv_taps_permute_f32: accumulate needs a destination")
+        out = torch.empty(shape, dtype=torch.float32, device=s.device)
+    assert out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.numel() == s.numel()
+    _lib.call("dhaug_conv_taps_permute_f32", _p(s), _p(out), N, Cin, k, int(bool(to_taps)), int(bool(accumulate)), _stream())
+    return out
+
+
+def tap_gather(x, nseq, t_in, C, k, dilation=1, stride=1, out_bf16=None, out_f32=None, want_bf16=None, want_f32=None):
+    """the A operand of a k-tap layer: x (nseq * t_in, >= C) fp32 / bf16 rows -> (out_bf16 | None, out_f32 | None), each
+    (nseq * t_out, k C) with out[s t_out + t, j C + c] = x[s t_in + t stride + j dilation, c] (dhaug_tap_gather).  By default the
+    output has x's type; out_bf16 / out_f32: write into these (row-strided views allowed)."""
+    if not x.is_cuda:
+        raise RuntimeError("dhaug op `tap_gather` needs a GPU tensor (no CPU fallback exists)")
+    if x.dim() != 2 or x.dtype not in (torch.float32, BF16) or x.shape[0] != nseq * t_in or x.shape[1] < C:
+        raise ValueError("tap_gather: x must be a fp32 or bf16 (%d, >= %d) matrix, got %s %s" % (nseq * t_in, C, x.dtype, tuple(x.shape)))
+    xb = x.dtype == BF16
+    if x.stride(1) != 1 or (x.stride(0) * x.element_size()) % 16 or x.data_ptr() % 16 or x.stride(0) < C:
+        x = x.contiguous()
+    want_bf16 = (xb or out_bf16 is not None) if want_bf16 is None else want_bf16
+    want_f32 = ((not xb and out_bf16 is None) or out_f32 is not None) if want_f32 is None else want_f32
+    t_out = (t_in - (k - 1) * dilation - 1) // stride + 1
+    rows = nseq * max(t_out, 0)
+    if want_bf16 and out_bf16 is None:
+        out_bf16 = torch.empty((rows, k * C), dtype=BF16, device=x.device)
+    if want_f32 and out_f32 is None:
+        out_f32 = torch.empty((rows, k * C), dtype=torch.float32, device=x.device)
+    for t, dt in ((out_bf16, BF16), (out_f32, torch.float32)):
+        assert t is None or (t.dtype == dt and t.is_cuda and t.dim() == 2 and t.stride(1) == 1 and t.shape[0] == rows)
+    _lib.call("dhaug_tap_gather", _p(x), int(xb), x.stride(0), nseq, t_in, C, k, dilation, stride, _p(out_bf16),
+              0 if out_bf16 is None else out_bf16.stride(0), _p(out_f32), 0 if out_f32 is None else out_f32.stride(0), _stream())
+    return out_bf16, out_f32

@@ -898,6 +898,45 @@ int dhaug_bn_fold(const float* W, int64_t ldw, const float* gamma, const float* 
                   const float* running_var, float eps, float* W_out, int64_t ld_out, float* bias_out, float* rstd_out, int64_t N,
                   int64_t K, void* stream);
 
+/* ------------------------------------------------------------------------------------------------------
+ * Multi-frame VideoPose posenets: the tap layout around the GEMMs (R/models_Fk_GAN/mulit_farme_videopose.py; csrc/dhaug_taps.hip)
+ * ----------------------------------------------------------------------------------------------------
+ * With activations as rows (batch-major, then time) a k-tap Conv1d is  A W2d^T,  W2d[n, j Cin + c] = W[n, c, j], where row r of A is
+ * the concatenation of the k input rows of output r's window.  With stride = k over non-overlapping frames (the training model) A is
+ * the input itself, viewed (M / k, k Cin); otherwise (dilation, the evaluation model) dhaug_tap_gather builds it.  Data movement only,
+ * vector stores, no atomics.
+ *
+ * dhaug_conv_taps_pack_bf16: W fp32 (N, Cin, k) contiguous ->
+ *     nt (N, ld_nt >= k Cin) bf16, nt[n, j Cin + c] = bf16(W[n, c, j])                          (the B operand of x W2d^T);
+ *     nn (k Cin, ld_nn >= ceil16 N) bf16, optional, nn[j Cin + c, n] = the same value, columns [N, ceil16 N) zero
+ *                                                                                                 (the B operand of g W2d).
+ *   Columns of nt at and beyond k Cin and of nn at and beyond ceil16 N are not touched.  Rounding as dhaug_cast_pad_bf16: the two
+ *   outputs equal dhaug_cast_pad_bf16 / dhaug_cast_transpose_bf16 of the permuted matrix bit for bit.  W is read once.
+ *   DHAUG_EINVAL: N or Cin < 0, a NULL W or nt, a leading dimension below its minimum.  DHAUG_EUNSUPPORTED: k outside [1, 16],
+ *   Cin % 16 != 0, N Cin k >= 2^31.  DHAUG_EALIGN: W, nt or nn not 16-byte aligned, ld_nt or ld_nn no multiple of 8.
+ * dhaug_conv_taps_permute_f32: fp32, both matrices contiguous, any N, Cin, k >= 1.
+ *     to_taps = 1:  dst (N, k Cin),  dst[n, j Cin + c]  = src[n, c, j]        (src (N, Cin, k); accumulate must be 0);
+ *     to_taps = 0:  dst (N, Cin, k), dst[n, c, j] (+)= src[n, j Cin + c]      (src (N, k Cin); accumulate 1 adds into dst, each thread
+ *                                                                              reading and writing only its own elements).
+ *   DHAUG_EINVAL: a negative size, a flag outside {0, 1}, accumulate with to_taps, a NULL pointer, src == dst.  DHAUG_EUNSUPPORTED:
+ *   N Cin k >= 2^31.  DHAUG_EALIGN: src not 4-byte, dst not 16-byte aligned.
+ * dhaug_tap_gather: x (nseq t_in, ld_x >= C) fp32 (x_bf16 = 0) or bf16 (1), nseq sequences of t_in rows each ->
+ *     out[(s t_out + t), j C + c] = x[(s t_in + t stride + j dilation), c],   t_out = (t_in - (k - 1) dilation - 1) / stride + 1,
+ *   to out_bf16 (nseq t_out, ld_ob >= k C) and / or out_f32 (nseq t_out, ld_of >= k C); at least one.  bf16 from bf16 is a copy, bf16
+ *   from fp32 rounds as dhaug_cast_pad_bf16, out_f32 needs fp32 input (DHAUG_EINVAL otherwise).  No window reads across a sequence
+ *   boundary: the last row read of sequence s is s t_in + t_in - 1 at most.  Columns at and beyond k C of the outputs are not touched.
+ *   DHAUG_EINVAL: a negative size, dilation or stride < 1, x_bf16 outside {0, 1}, a NULL x, no output, a leading dimension below
+ *   its minimum.  DHAUG_EUNSUPPORTED: C % 16 != 0, k outside [1, 16], t_in < (k - 1) dilation + 1 (t_out < 1), nseq t_in >= 2^31,
+ *   k C >= 2^28, dilation or stride >= 2^30.  DHAUG_EALIGN: a pointer not 16-byte aligned, rows not 16-byte aligned (ld_x, ld_ob % 8
+ *   for bf16, ld_x, ld_of % 4 for fp32).
+ * All three: an empty problem (N or Cin = 0, for the permutation also k = 0; nseq or C = 0) is a no-op that looks at no pointer. */
+int dhaug_conv_taps_pack_bf16(const float* W, int64_t N, int64_t Cin, int k, uint16_t* nt, int64_t ld_nt, uint16_t* nn,
+                              int64_t ld_nn, void* stream);
+int dhaug_conv_taps_permute_f32(const float* src, float* dst, int64_t N, int64_t Cin, int k, int to_taps, int accumulate,
+                                void* stream);
+int dhaug_tap_gather(const void* x, int x_bf16, int64_t ld_x, int64_t nseq, int64_t t_in, int64_t C, int k, int dilation,
+                     int stride, uint16_t* out_bf16, int64_t ld_ob, float* out_f32, int64_t ld_of, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
