@@ -16,10 +16,8 @@
 #if defined(T4_ABL_NOSTORE) || defined(T4_ABL_NOCOMPUTE) || defined(ABL_NOWRITE) || defined(ABL_NOREAD) || defined(ABL_NOWLOAD) || \
     defined(SAVE_ABL_NOSTORE) || defined(SAVE_ABL_BRANCH) || defined(SAVE_ABL_NOBITS) || defined(SAVE_ABL_NONANSAFE) || defined(SAVE_ABL_NULLSTORES) || defined(MOVE_BATCH_OVERRIDE) || defined(LOAD_ABL_NOROWS32) || \
     defined(DHAUG_MLP_TIMING) || defined(DHAUG_MLP_TIMING_UNITS) || defined(DHAUG_STAMP_TID) || defined(DHAUG_PIPE_TIMING) || defined(DHAUG_TOP_TIMING) || \
-    defined(W_NO_XCD_MAP) || defined(X3_NWAVES) || defined(X3_SPREAD) || defined(X3_RING) || defined(X3_TIMING) || \
-    defined(X3_STAMP_TID) || defined(X3_REG_STASH) || defined(X3_WS_NT) || defined(X3_EPI_FENCE) || defined(X3_WRITE128) || \
-    defined(X3_ABL_NOSPLIT) || defined(X3_ABL_NOWRITE) || defined(X3_ABL_NOWS) || defined(X3_ABL_NOREAD) || \
-    defined(X3_ABL_NOWLOAD) || defined(X3_ABL_NOEPI) || defined(X3_AB_SPLIT) || defined(X3_PRIO_SEL) || \
+    defined(W_NO_XCD_MAP) || defined(X3_TIMING) || defined(X3_STAMP_TID) || \
+    defined(X3_ABL_NOSPLIT) || defined(X3_ABL_NOWRITE) || defined(X3_ABL_NOREAD) || defined(X3_ABL_NOWLOAD) || defined(X3_ABL_NOEPI) || \
     defined(P8_ABL_NOMMA) || defined(P8_ABL_NOREAD) || defined(P8_ABL_NOCOPY) || defined(P8_ABL_NOEPI) || defined(P8_ABL_NOSTAGGER) || \
     defined(P8_ABL_NOPRIO) || defined(P8_TIMING)
 #error "a development / ablation switch is defined without -DDHAUG_ABLATION_BUILD: this would build a library with wrong results"

@@ -229,7 +229,8 @@ class FusedNet:
 
 def launch(units, M, mode):
     if mode == "f16x3":
-        # residuals and parked partial sums wait in a global workspace (DHAUG_MLP_X3_WORKSPACE_BYTES, include/dhaug.h).  One per
+        # a parked partial sum waits in a global workspace (DHAUG_MLP_X3_WORKSPACE_BYTES, include/dhaug.h; residuals stay in the
+        # kernel's registers, but a program that has any must pass the workspace too).  One per
         # launch from the caching allocator, i.e. stream-ordered: launches on different streams never share one, and a
         # hipGraph capture gets its own from the graph's pool.
         dev = torch.device("cuda", torch.cuda.current_device())

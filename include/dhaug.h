@@ -669,10 +669,13 @@ int dhaug_mlp_forward(const dhaug_mlp_unit* units, int nunits, int64_t M, void* 
  * layers are fp32 nn.Linear: R/models_Fk_GAN/Fk_discriminator.py:180-201,253-266, R/models_Fk_GAN/Fk_generator.py:115-119;
  * tolerance 1e-4 relative on the logits) at three matrix instructions per k-step.  128-row batch tiles; the activation lives
  * in ONE hi / lo image in LDS that every layer updates in place, so the three buffer ids of a program are virtual: the
- * library checks that every value a unit reads is where the kernel can find it (the image for a source, the workspace for a
- * residual) and returns DHAUG_EUNSUPPORTED otherwise.  Values that a later unit adds as a RESIDUAL wait in a global workspace
- * (fp32, written and read back by the same lane): a program with residuals passes g = a 16-byte aligned buffer of
- * DHAUG_MLP_X3_WORKSPACE_BYTES, shared with no concurrent launch, in its GEMM units that are not outputs (any content).
+ * library checks that every value a unit reads is where the kernel can find it (the image for a source; for a residual the
+ * registers of the lane that produced it, or the workspace) and returns DHAUG_EUNSUPPORTED otherwise.  A value that a later
+ * unit adds as a RESIDUAL stays in registers.  Only a partial sum that is PARKED while another branch of the program uses the
+ * image and those registers (a result that is added later and read as a source by nobody) waits in a global workspace (fp32,
+ * written and read back by the same lane; only the second half of the buffer is touched).  A program with residuals or a
+ * parked sum passes g = a 16-byte aligned buffer of DHAUG_MLP_X3_WORKSPACE_BYTES, shared with no concurrent launch, in its
+ * GEMM units that are not outputs (any content).
  * Differences from dhaug_mlp_forward: weights come from dhaug_pack_wfrag_f16x2; only LOAD_F32 (cols and ld even, 8-byte
  * aligned base), LOAD_KCS and GEMM units; no second source; no F_DOT_OUT (a 1-wide logit layer is an OUT_F32 unit).
  * dhaug_pack_wfrag_f16x2: dst[(((slice*ksteps + ks)*2 + piece)*64 + lane)*8 + j] = piece(W[32 slice + (lane&31)][k0 + 16 ks +

@@ -65,7 +65,7 @@ def test_ablation_switches_need_an_ablation_build(tmp_path):
     base = [G.HIPCC, "-x", "hip", "--cuda-host-only", "-fsyntax-only", "-I" + os.path.join(ROOT, "include"), "-I" + G.CSRC]
     ok = subprocess.run(base + [str(src)], capture_output=True, text=True)
     assert ok.returncode == 0, ok.stderr[-2000:]
-    for d in ("X3_ABL_NOSPLIT", "ABL_NOWRITE", "SAVE_ABL_NULLSTORES", "T4_ABL_NOCOMPUTE", "X3_NWAVES=4", "DHAUG_MLP_TIMING"):
+    for d in ("X3_ABL_NOSPLIT", "ABL_NOWRITE", "SAVE_ABL_NULLSTORES", "T4_ABL_NOCOMPUTE", "X3_TIMING", "DHAUG_MLP_TIMING"):
         bad = subprocess.run(base + ["-D" + d, str(src)], capture_output=True, text=True)
         assert bad.returncode != 0 and "DHAUG_ABLATION_BUILD" in bad.stderr, d
         good = subprocess.run(base + ["-D" + d, "-DDHAUG_ABLATION_BUILD", str(src)], capture_output=True, text=True)
@@ -73,12 +73,16 @@ def test_ablation_switches_need_an_ablation_build(tmp_path):
     # the shipped sources name no switch the guard does not know: every *_ABL_* / X3_* / timing macro tested by an #if / #ifdef
     guard = open(os.path.join(G.CSRC, "dhaug_common.h")).read()
     known = set(re.findall(r"defined\((\w+)\)", guard))
-    internal = {"X3_SHAPE16", "X3_NW", "X3_MT", "X3_BM", "X3_B16", "X3_THREADS", "X3_LDS_BYTES", "X3_MAX_UNITS", "X3_CASE", "X3_CASE_ADD",
+    internal = {"X3_NW", "X3_MT", "X3_BM", "X3_B16", "X3_THREADS", "X3_LDS_BYTES", "X3_MAX_UNITS", "X3_CASE", "X3_CASE_ADD",
                 "X3_CASE_STASH", "X3_STAMP", "X3_WORKSPACE_BYTES"}                     # defined by the sources themselves, unconditionally
     for path in sorted(p for p in os.listdir(G.CSRC) if p.endswith((".hip", ".h"))):
         text = open(os.path.join(G.CSRC, path)).read()
         for mac in set(re.findall(r"^\s*#\s*(?:if|ifdef|ifndef|elif)[^\n]*?\b((?:\w*_ABL_\w+|ABL_\w+|X3_\w+|\w*TIMING\w*|\w+_OVERRIDE|W_NO_\w+))\b", text, re.M)):
             assert mac in known or mac in internal, (path, mac)
+    # ... and the guard knows no switch that the sources have lost: every name in it occurs in another file of csrc/
+    others = "".join(open(os.path.join(G.CSRC, p)).read() for p in sorted(os.listdir(G.CSRC)) if p.endswith((".hip", ".h")) and p != "dhaug_common.h")
+    for mac in sorted(known):
+        assert re.search(r"\b%s\b" % mac, others), mac
 
 
 def test_argument_errors_are_returned_not_thrown(built):

@@ -6,7 +6,7 @@ P=dh-aug-dh-forward-kinematics-model-driven-augmentation-for-3d-human-pose-estim
 O=tools/_timing
 mkdir -p $O
 F="--offload-arch=gfx950 -DDHAUG_ABLATION_BUILD -O3 -fPIC -ffp-contract=fast -Iinclude -I$P/csrc"
-VARIANTS=${VARIANTS:-"prio0:-DX3_PRIO_SEL=0 prio1:-DX3_PRIO_SEL=1 prio2:-DX3_PRIO_SEL=2"}
+VARIANTS=${VARIANTS:-"abl_nosplit:-DX3_ABL_NOSPLIT abl_nowrite:-DX3_ABL_NOWRITE abl_noread:-DX3_ABL_NOREAD abl_nowload:-DX3_ABL_NOWLOAD abl_noepi:-DX3_ABL_NOEPI timing:-DX3_TIMING"}
 for v in $VARIANTS; do
   n=${v%%:*}; d=${v#*:}
   /opt/rocm/bin/hipcc $F ${d//,/ } -c $P/csrc/dhaug_mlp_x3.hip -o $O/x3_$n.o &
