@@ -132,7 +132,7 @@ def _w_nt(W, Kp, prec):
 
 def _w_nn(W, prec, mode=1):
     """B operand of g W (= g (W^T)^T): (K, Np) bf16, or (K, 3Np).  mode 0: the split in the ACTIVATION-side layout, for a g that
-    comes in the weight-side layout (the product pairs are symmetric in the two layouts: critic_step._Math.mm)."""
+    comes in the weight-side layout (the product pairs are symmetric in the two layouts: critic_step._SplitMath.mm)."""
     ent = _pack(W)
     if prec == "bf16":
         if ent.nn is None:
@@ -245,7 +245,7 @@ def _raw_outer(g, x, N, K, prec, colsum=None, out=None, split=None):
     # layout, row T m + t of the two carries exactly the t-th product pair (dhaug_split_bf16: [hi|mid|hi|mid|lo|hi] against
     # [hi|hi|mid|mid|hi|lo]), so sum_{m,t} g''[Tm+t]^T x''[Tm+t] is the six-term (three-term) product.  (Before: one contraction
     # per pair on column blocks of two activation-side splits -- six launches, six partial sums.)
-    if split is not None:                      # (the caller holds the operands' splits already: critic_step._Math)
+    if split is not None:                      # (the caller holds the operands' splits already: critic_step._SplitMath)
         g1, x3 = split
     else:
         g1 = ops.split_bf16(g, 1, T, Np)

@@ -47,7 +47,7 @@ _TN_SIDE = {}
 # 224 -> 6.39, 256 -> 6.40 (four runs, 6.35 - 6.44); the video iteration does not care (13.25 either way)
 TN_SIDE_WGS = int(os.environ.get("DHAUG_TN_SIDE_WGS", "256"))
 
-# the layers of independent branches at the same depth as ONE launch (_Math.mm_group, dhaug_gemm_bf16_group): a motion critic's four /
+# the layers of independent branches at the same depth as ONE launch (_Bf16Math.mm_group, dhaug_gemm_bf16_group): a motion critic's four /
 # two branch layers.  On by default since round 5 (DHAUG_NO_NT_GROUP=1: one launch per layer): the grouped launch runs on 128 x 128
 # tiles -- four 1 536 x 1000 x 1000 layers are 384 workgroups, ONE round of the card's slots, half the staged bytes of 64 x 64 tiles.
 # (Round 4's form, the same launch on 64 x 64 tiles = 1 536 workgroups: 35 us alone against 4 x 12.7, but 17.2 ms per video iteration
@@ -92,23 +92,51 @@ def capture_root():
     return cur.cuda_stream == CAPTURE_ROOT and (cur.device.index, cur.cuda_stream) in _TN_SIDE
 
 
-class _Math:
-    """the three products of a layer in one arithmetic; activations are bf16 (M, ceil16 n) in 'bf16', fp32 (M, n) otherwise"""
+class _MathBase:
+    """the three products of a layer in one arithmetic (math_for): the queue of weight-gradient contractions and its launches"""
 
     def __init__(self, prec):
-        self.prec, self.bf16 = prec, prec == "bf16"
-        self.T = 1 if self.bf16 else A.TERMS[prec]
+        self.prec = prec
         self.tn = []                                 # weight-gradient contractions waiting for the grouped launch (flush)
-        self.tn2, self._tn_slots = [], set()         # split-operand arithmetic: second contributions to a slot already in self.tn
-        self._splits, self._split_src = [], []       # split-operand arithmetic: (address, rows, cols, mode, split) of this step
-        self._casts = {}                             # bf16: the casts of fp32 inputs made in this step
         self._side = None                            # (stream, items) of sweep 4's part under way on a side stream (flush_side)
 
-    def width(self, n):
-        return ceil16(n) if self.bf16 else n
-
     def empty(self, M, n, dev):
-        return torch.empty((M, self.width(n)), dtype=BF16 if self.bf16 else torch.float32, device=dev)
+        return torch.empty((M, self.width(n)), dtype=self.dtype, device=dev)
+
+    def flush(self):
+        """launch the collected weight-gradient contractions (before the optimizer step reads the gradient bucket)"""
+        self.join()                          # (both parts accumulate into the same gradient slots: never concurrently)
+        if self.tn:
+            ops.gemm_tn_group(self.tn)
+            self.tn = []
+
+    def flush_side(self):
+        """the same on a side stream of the current one (join() / flush() makes the current stream wait for it): the
+        operands stay referenced until then"""
+        if not self.tn:
+            return
+        cur = torch.cuda.current_stream()
+        st = tn_side_stream(cur)
+        st.wait_stream(cur)
+        with torch.cuda.stream(st):
+            ops.gemm_tn_group(self.tn, max_workgroups=TN_SIDE_WGS)
+        self._side = (st, self.tn)
+        self.tn = []
+
+    def join(self):
+        if self._side is not None:
+            torch.cuda.current_stream().wait_stream(self._side[0])
+            self._side = None
+
+
+class _Bf16Math(_MathBase):
+    """'bf16', the throughput arithmetic: activations are bf16 (M, ceil16 n)"""
+    bf16, dtype = True, BF16
+    width = staticmethod(ceil16)
+
+    def __init__(self, prec):
+        super().__init__(prec)
+        self._casts = {}                             # the casts of fp32 inputs made in this step
 
     def empty_blocks(self, M, nb, Dw, dev):
         """(M, nb * Dw) buffer whose Dw-wide column blocks become A operands of GEMMs with K = ceil16(Dw) (the cotangent of a
@@ -116,17 +144,15 @@ class _Math:
         read 16 - Dw % 16 columns beyond the block -- against zero columns of the weights' operand copy, so the values only have to be
         FINITE: inside the buffer they are the next block's / the next row's cotangents, but the last row of the last block would be
         read beyond the allocation (found in round 5 with torch.empty poisoned: NaN x 0).  Such a buffer gets one more row, its head zeroed."""
-        if not self.bf16 or Dw % 16 == 0:
+        if Dw % 16 == 0:
             return None                              # (no over-read: the product allocates its output as usual)
-        buf = torch.empty((M + 1, self.width(nb * Dw)), dtype=BF16, device=dev)
+        buf = torch.empty((M + 1, ceil16(nb * Dw)), dtype=BF16, device=dev)
         buf[M, :16].zero_()
         return buf[:M]
 
-    def _a(self, a, k):
-        """activation-side operand of a (fp32 (M,k) network input / bf16 hidden / fp32 hidden)"""
-        if self.bf16:
-            return a if a.dtype == BF16 else self.cast(a, ceil16(k))
-        return self.split0(a, k)
+    def seed_operand(self, s):
+        """the logit cotangents (rows, 1) fp32 as the backward chain's first operand"""
+        return ops.cast_pad_bf16(s, 16)
 
     def cast(self, a, width):
         """bf16 copy of an fp32 network input / tangent seed, made once per tensor and step (the tangent seeds of a branch are an
@@ -141,8 +167,116 @@ class _Math:
     def seed_cast(self, a, width, b):
         """b IS the bf16 copy cast(a, width) would make -- its producer wrote it beside a (ops.gp_assemble / gp_penalty, the KCS
         operand of ops.kcs_forward): registered, no launch (the casts were 8 launches and ~90 us of a single-frame iteration)"""
-        if self.bf16 and b is not None and b.dtype == BF16 and tuple(b.shape) == (a.shape[0], width):
+        if b is not None and b.dtype == BF16 and tuple(b.shape) == (a.shape[0], width):
             self._casts[(a.data_ptr(), tuple(a.shape), tuple(a.stride()), width)] = (b, a)
+
+    def mm(self, a, W, orient, bias=None, res=None, act=NONE, slope=0.0, mask=None, mask_act=NONE, out=None, out_f32=False):
+        """(a @ W^T if orient == 'nt' else a @ W) + bias + res, then act(.) or, with `mask`, * mask_act'(mask).
+        a: fp32 (M, k) network input or bf16 hidden activation."""
+        N, K = W.shape
+        n, k = (N, K) if orient == "nt" else (K, N)
+        kp = ceil16(k)
+        Bop = A._w_nt(W, kp, self.prec) if orient == "nt" else A._w_nn(W, self.prec)
+        a_op = a if a.dtype == BF16 else self.cast(a, kp)
+        masked = mask is not None and mask_act != NONE and not out_f32
+        if (masked and orient == "nn" and N == 1 and a.dtype == BF16 and res is None and bias is None
+                and mask.stride(0) % 8 == 0 and mask.shape[1] >= ceil16(K) and ceil16(K) <= 1024):
+            # the logit layer's input cotangent: seed (rows,1) x weight row (1,K), masked -- a streaming kernel, not a K = 1 GEMM
+            return ops.rank1_mask(a, Bop[:, 0], mask, K, mask_act, slope, out=out)
+        rb = res if (res is not None and res.dtype == BF16) else None
+        rf = res if (res is not None and res.dtype != BF16) else None
+        if masked and rf is None and bias is None:
+            return ops.gemm_nt_dmask(a_op, Bop, n, kp, mask, mask_act, slope, res_bf16=rb, out=out)
+        if masked:
+            y, _ = ops.gemm_nt(a_op, Bop, n, kp, bias=bias, res_bf16=rb, res_f32=rf, out_bf16=True, n_pad=ceil16(n), c_bf16=out)
+            w = min(y.shape[1], mask.shape[1])           # (a column block of a wider buffer carries no pad columns)
+            ya, ma = (y, mask) if (y.shape[1] == w and mask.shape[1] == w) else (y[:, :w], mask[:, :w])
+            ops.act_backward(ya, ma, mask_act, slope, out=ya)
+            return y
+        cb, cf = ops.gemm_nt(a_op, Bop, n, kp, bias=bias, res_bf16=rb, res_f32=rf, act=act, slope=slope,
+                             out_bf16=not out_f32, n_pad=ceil16(n), out_f32=out_f32, c_bf16=None if out_f32 else out,
+                             c_f32=out if out_f32 else None)
+        return cf if out_f32 else cb
+
+    def mm_group(self, calls):
+        """The products of the SAME layer position in several independent branches: `calls` are keyword dicts for mm().  Where
+        every call is a plain or mask-fused generic GEMM of one shape, they are ONE launch (ops.gemm_nt_group: a motion
+        critic's four / two branch layers); otherwise they run one by one."""
+        if not (NT_GROUP and 2 <= len(calls) <= ops.NT_GROUP_MAX):
+            return [self.mm(**kw) for kw in calls]
+        members, shape = [], None
+        for kw in calls:
+            a, W, orient = kw["a"], kw["W"], kw["orient"]
+            N, K = W.shape
+            n, k = (N, K) if orient == "nt" else (K, N)
+            kp = ceil16(k)
+            res, mask, mask_act = kw.get("res"), kw.get("mask"), kw.get("mask_act", NONE)
+            masked = mask is not None and mask_act != NONE
+            out = kw.get("out")
+            ok = (a.dtype == BF16 and (a.shape[1] == kp or (a.shape[1] == k and a.stride(0) >= kp)) and a.stride(1) == 1
+                  and not kw.get("out_f32", False) and (res is None or res.dtype == BF16)
+                  and n > 256 and kp > 256 and (out is None or (out.dtype == BF16 and out.stride(1) == 1))
+                  and (not masked or (kw.get("bias") is None and kw.get("act", NONE) == NONE and mask.dtype == BF16
+                                      and getattr(mask, "_dhaug_bits", None) is None and getattr(mask, "_dhaug_bits_cols", None) is None)))
+            sh = (a.shape[0], n, kp, masked)
+            if not ok or (shape is not None and sh != shape):
+                return [self.mm(**kw) for kw in calls]
+            shape = sh
+            Bop = A._w_nt(W, kp, self.prec) if orient == "nt" else A._w_nn(W, self.prec)
+            members.append(dict(A=a, B=Bop, N=n, K=kp, bias=kw.get("bias"), res_bf16=res, act=kw.get("act", NONE), slope=kw.get("slope", 0.0),
+                                dmask=mask if masked else None, dmask_act=mask_act if masked else NONE, dmask_slope=kw.get("slope", 0.0),
+                                out=out, n_pad=ceil16(n)))
+        return ops.gemm_nt_group(members)
+
+    def flush(self):
+        super().flush()
+        self._casts = {}
+
+    def can_split(self, B):
+        """sweep 4 in two parts (TN_SPLIT): whole 32-row stages in both parts, batches long enough for the grouped launch"""
+        # (inside a hipGraph capture only on the stream the capture was begun on: hipStreamEndCapture of this HIP release
+        # crashes on a fork inside a fork, or on an edge between sibling branches -- a step that runs on a forked stream
+        # there, concurrent critics, keeps sweep 4 in one part)
+        return (TN_SPLIT and B % 32 == 0 and ops.tn_group_ok(B, 1, 1, 0)
+                and (not torch.cuda.is_current_stream_capturing() or capture_root()))
+
+    def outer(self, g, x, N, K, wslot, bslot=None, colsum_rows=None):
+        """wslot (N,K) += g^T x;  bslot (N) += column sums of g over rows [0, colsum_rows) (all rows by default; through the
+        pairing column-sum kernel when N < 16)"""
+        gb = g if g.dtype == BF16 else self.cast(g, ceil16(N))
+        xb = x if x.dtype == BF16 else self.cast(x, ceil16(K))
+        narrow = N < 16
+        M = gb.shape[0]
+        cr = M if colsum_rows is None else colsum_rows
+        cs = bslot if (bslot is not None and not narrow) else None
+        if ops.tn_group_ok(M, min(N, 256), min(K, 256), cr):
+            # joins the step's grouped launch (a DenseDim-1000 layer is 4 x 4 blocks of 256 x 256: ops.gemm_tn_group hands it
+            # over whole where the group has blocks enough to fill the card, block by block otherwise; the bias sums ride
+            # with the first column block of every row block)
+            self.tn.append(ops.TnItem(A=gb, B=xb, N1=N, N2=K, out=wslot, colsum=cs, colsum_rows=cr if cs is not None else 0, M=M))
+        else:
+            ops.gemm_tn(gb, xb, N, K, colsum=cs, out=wslot, accumulate=True, colsum_rows=colsum_rows)
+        if bslot is not None and narrow:
+            ops.colsum(gb if colsum_rows is None else gb[:colsum_rows], N=N, out=bslot, accumulate=True)
+
+
+class _SplitMath(_MathBase):
+    """'bf16x3' / 'bf16x6', split operands (parity tests): activations are fp32 (M, n); strided views are staged through
+    contiguous copies"""
+    bf16, dtype = False, torch.float32
+
+    def __init__(self, prec):
+        super().__init__(prec)
+        self.T = A.TERMS[prec]
+        self.tn2, self._tn_slots = [], set()         # second contributions to a slot already in self.tn
+        self._splits, self._split_src = [], []       # (address, rows, cols, mode, split) of this step
+
+    # what is degenerate here: fp32 operands travel as they are (no pad columns, no cast of the logit cotangents, no bf16 copy to
+    # register), no column block is over-read, layers run one by one and sweep 4 stays in one part
+    width = seed_operand = staticmethod(lambda v: v)
+    seed_cast = empty_blocks = lambda self, *a: None
+    mm_group = lambda self, calls: [self.mm(**kw) for kw in calls]
+    can_split = lambda self, B: False
 
     def split0(self, a, k, mode=0):
         """the activation-side split of fp32 a (rows, k) -- made ONCE per tensor and step: a layer's input, cotangent and tangent
@@ -164,7 +298,7 @@ class _Math:
     def planes_ok(self, k):
         """an fp32 operand k wide may travel as three planes (see PLANES)"""
         kp = ceil16(k)
-        return PLANES and not self.bf16 and self.T == 6 and kp >= 64 and (kp & (kp - 1)) == 0
+        return PLANES and self.T == 6 and kp >= 64 and (kp & (kp - 1)) == 0
 
     def cached_split(self, a, k, mode):
         """the split of (a row range of) this tensor made earlier in the step, or None"""
@@ -194,14 +328,15 @@ class _Math:
         return y
 
     def mm(self, a, W, orient, bias=None, res=None, act=NONE, slope=0.0, mask=None, mask_act=NONE, out=None, out_f32=False):
-        """(a @ W^T if orient == 'nt' else a @ W) + bias + res, then act(.) or, with `mask`, * mask_act'(mask)."""
+        """(a @ W^T if orient == 'nt' else a @ W) + bias + res, then act(.) or, with `mask`, * mask_act'(mask); fp32 (M, k) in,
+        fp32 out whatever out_f32 says."""
         N, K = W.shape
         n, k = (N, K) if orient == "nt" else (K, N)
         kp = ceil16(k)
-        # split-operand arithmetic, backward chain (orient "nn"): the cotangent is split ONCE, in the weight-side layout -- the
-        # layout sweep 4 contracts it in (autograd_ops._raw_outer) -- and meets the weights in the activation-side layout
-        swap = (not self.bf16) and orient == "nn"
-        f32rows = (not self.bf16) and a.dtype == torch.float32 and a.dim() == 2 and a.stride(1) == 1
+        # backward chain (orient "nn"): the cotangent is split ONCE, in the weight-side layout -- the layout sweep 4 contracts it
+        # in (autograd_ops._raw_outer) -- and meets the weights in the activation-side layout
+        swap = orient == "nn"
+        f32rows = a.dtype == torch.float32 and a.dim() == 2 and a.stride(1) == 1
         # a result that is itself an operand of plane width (the next layer's input, sweep 4's) leaves the GEMM with its planes beside it
         emit = PLANES_OUT and self.planes_ok(n) and ceil16(n) == n and (out is None or out.is_contiguous())
         plan = None                                  # (x_order, mode of the activation-side split, six-segment operand, emit)
@@ -218,28 +353,7 @@ class _Math:
             r = ops.gemm_nt_planes(self.split0(a, k, mode), Bop, n, kp, bias=bias, res_f32=resc, act=act, slope=slope, dmask_f32=dm,
                                    dmask_act=mask_act if dm is not None else NONE, dmask_slope=slope, out=out, x_order=x_order, planes_out=emit)
             return self._register_planes(r[0], n, r[1]) if emit else r
-        a_op = self.split0(a, k, 1) if swap else self._a(a, k)
-        if (self.bf16 and orient == "nn" and N == 1 and a.dtype == BF16 and res is None and bias is None
-                and mask is not None and mask_act != NONE and not out_f32 and mask.stride(0) % 8 == 0 and mask.shape[1] >= ceil16(K)
-                and ceil16(K) <= 1024):
-            # the logit layer's input cotangent: seed (rows,1) x weight row (1,K), masked -- a streaming kernel, not a K = 1 GEMM
-            return ops.rank1_mask(a, A._w_nn(W, self.prec)[:, 0], mask, K, mask_act, slope, out=out)
-        if self.bf16:
-            rb = res if (res is not None and res.dtype == BF16) else None
-            rf = res if (res is not None and res.dtype != BF16) else None
-            if mask is not None and mask_act != NONE and not out_f32 and rf is None and bias is None:
-                return ops.gemm_nt_dmask(a_op, Bop, n, kp, mask, mask_act, slope, res_bf16=rb, out=out)
-            if mask is not None and mask_act != NONE and not out_f32:
-                y, _ = ops.gemm_nt(a_op, Bop, n, kp, bias=bias, res_bf16=rb, res_f32=rf, out_bf16=True, n_pad=ceil16(n), c_bf16=out)
-                w = min(y.shape[1], mask.shape[1])           # (a column block of a wider buffer carries no pad columns)
-                ya, ma = (y, mask) if (y.shape[1] == w and mask.shape[1] == w) else (y[:, :w], mask[:, :w])
-                ops.act_backward(ya, ma, mask_act, slope, out=ya)
-                return y
-            cb, cf = ops.gemm_nt(a_op, Bop, n, kp, bias=bias, res_bf16=rb, res_f32=rf, act=act, slope=slope,
-                                 out_bf16=not out_f32, n_pad=ceil16(n), out_f32=out_f32, c_bf16=None if out_f32 else out,
-                                 c_f32=out if out_f32 else None)
-            return cf if out_f32 else cb
-        # split-operand arithmetic (parity tests): fp32 activations; strided views are staged through contiguous copies
+        a_op = self.split0(a, k, 1 if swap else 0)
         if res is not None and not res.is_contiguous():
             res = res.contiguous()
         masked = mask is not None and mask_act != NONE
@@ -256,94 +370,15 @@ class _Math:
             return out
         return cf
 
-    def mm_group(self, calls):
-        """The products of the SAME layer position in several independent branches: `calls` are keyword dicts for mm().  In bf16,
-        where every call is a plain or mask-fused generic GEMM of one shape, they are ONE launch (ops.gemm_nt_group: a motion
-        critic's four / two branch layers); otherwise they run one by one."""
-        if not (self.bf16 and NT_GROUP and 2 <= len(calls) <= ops.NT_GROUP_MAX):
-            return [self.mm(**kw) for kw in calls]
-        members, shape = [], None
-        for kw in calls:
-            a, W, orient = kw["a"], kw["W"], kw["orient"]
-            N, K = W.shape
-            n, k = (N, K) if orient == "nt" else (K, N)
-            kp = ceil16(k)
-            res, mask, mask_act = kw.get("res"), kw.get("mask"), kw.get("mask_act", NONE)
-            masked = mask is not None and mask_act != NONE
-            out = kw.get("out")
-            ok = (a.dtype == BF16 and (a.shape[1] == kp or (a.shape[1] == k and a.stride(0) >= kp)) and a.stride(1) == 1
-                  and not kw.get("out_f32", False) and (res is None or res.dtype == BF16)
-                  and n > 256 and kp > 256 and (out is None or (out.dtype == BF16 and out.stride(1) == 1))
-                  and (not masked or (kw.get("bias") is None and kw.get("act", NONE) == NONE and mask.dtype == BF16
-                                      and getattr(mask, "_dhaug_bits", None) is None and getattr(mask, "_dhaug_bits_cols", None) is None)))
-            sh = (a.shape[0], n, kp, masked)
-            if not ok or (shape is not None and sh != shape):
-                return [self.mm(**kw) for kw in calls]
-            shape = sh
-            Bop = A._w_nt(W, kp, self.prec) if orient == "nt" else A._w_nn(W, self.prec)
-            members.append(dict(A=a, B=Bop, N=n, K=kp, bias=kw.get("bias"), res_bf16=res, act=kw.get("act", NONE), slope=kw.get("slope", 0.0),
-                                dmask=mask if masked else None, dmask_act=mask_act if masked else NONE, dmask_slope=kw.get("slope", 0.0),
-                                out=out, n_pad=ceil16(n)))
-        return ops.gemm_nt_group(members)
-
     def flush(self):
-        """launch the collected weight-gradient contractions (before the optimizer step reads the gradient bucket)"""
-        self.join()                          # (both parts accumulate into the same gradient slots: never concurrently)
-        if self.tn:
-            ops.gemm_tn_group(self.tn)
-            self.tn = []
+        super().flush()
         if self.tn2:
             ops.gemm_tn_group(self.tn2)
         self.tn2, self._tn_slots = [], set()
-        self._splits, self._split_src, self._casts = [], [], {}
-
-    def flush_side(self):
-        """the same on a side stream of the current one (join() / flush() makes the current stream wait for it): the
-        operands stay referenced until then"""
-        if not self.tn:
-            return
-        cur = torch.cuda.current_stream()
-        st = tn_side_stream(cur)
-        st.wait_stream(cur)
-        with torch.cuda.stream(st):
-            ops.gemm_tn_group(self.tn, max_workgroups=TN_SIDE_WGS)
-        self._side = (st, self.tn)
-        self.tn = []
-
-    def join(self):
-        if self._side is not None:
-            torch.cuda.current_stream().wait_stream(self._side[0])
-            self._side = None
-
-    def can_split(self, B):
-        """sweep 4 in two parts (TN_SPLIT): bf16, whole 32-row stages in both parts, batches long enough for the grouped launch"""
-        # (inside a hipGraph capture only on the stream the capture was begun on: hipStreamEndCapture of this HIP release
-        # crashes on a fork inside a fork, or on an edge between sibling branches -- a step that runs on a forked stream
-        # there, concurrent critics, keeps sweep 4 in one part)
-        return (self.bf16 and TN_SPLIT and B % 32 == 0 and ops.tn_group_ok(B, 1, 1, 0)
-                and (not torch.cuda.is_current_stream_capturing() or capture_root()))
+        self._splits, self._split_src = [], []
 
     def outer(self, g, x, N, K, wslot, bslot=None, colsum_rows=None):
-        """wslot (N,K) += g^T x;  bslot (N) += column sums of g over rows [0, colsum_rows) (all rows by default; through the
-        pairing column-sum kernel when N < 16)"""
-        if self.bf16:
-            gb = g if g.dtype == BF16 else self.cast(g, ceil16(N))
-            xb = x if x.dtype == BF16 else self.cast(x, ceil16(K))
-            narrow = N < 16
-            M = gb.shape[0]
-            cr = M if colsum_rows is None else colsum_rows
-            if ops.tn_group_ok(M, min(N, 256), min(K, 256), cr):
-                # joins the step's grouped launch (a DenseDim-1000 layer is 4 x 4 blocks of 256 x 256: ops.gemm_tn_group hands it
-                # over whole where the group has blocks enough to fill the card, block by block otherwise; the bias sums ride
-                # with the first column block of every row block)
-                cs = bslot if (bslot is not None and not narrow) else None
-                self.tn.append((gb, xb, N, K, wslot, cs, cr if cs is not None else 0, True, M, None, None))
-            else:
-                ops.gemm_tn(gb, xb, N, K, colsum=bslot if (bslot is not None and not narrow) else None, out=wslot, accumulate=True,
-                            colsum_rows=colsum_rows)
-            if bslot is not None and narrow:
-                ops.colsum(gb if colsum_rows is None else gb[:colsum_rows], N=N, out=bslot, accumulate=True)
-            return
+        """wslot (N,K) += g^T x;  bslot (N) += column sums of g"""
         rowm = lambda t: t if (t.dim() == 2 and t.stride(1) == 1) else t.contiguous()      # (row-major, any row pitch)
         gc, xc = rowm(g), rowm(x)
         TM, Np, Kp = self.T * gc.shape[0], ceil16(N), ceil16(K)
@@ -356,7 +391,7 @@ class _Math:
             # the split-operand contraction (ONE contraction over T * M rows: autograd_ops._raw_outer) joins the step's grouped launch
             # like a bf16 one.  A second contribution to the same gradient (the interpolated rows' part) waits for a second launch:
             # the items of one launch are summed into their slots concurrently.
-            item = (g1.view(-1, Np), x3.view(-1, Kp), N, K, wslot, None, 0, True, TM, None, None, pa, pb)
+            item = ops.TnItem(A=g1.view(-1, Np), B=x3.view(-1, Kp), N1=N, N2=K, out=wslot, M=TM, planes_a=pa, planes_b=pb)
             key = wslot.data_ptr()
             if key in self._tn_slots:
                 self.tn2.append(item)
@@ -368,6 +403,11 @@ class _Math:
             A._raw_outer(gc, xc, N, K, self.prec, out=wslot, split=(g1, x3))
         if bslot is not None:
             ops.colsum(g if g.is_contiguous() else g.contiguous(), N=N, out=bslot, accumulate=True)
+
+
+def math_for(prec):
+    """the arithmetic of a step: 'bf16', or the split-operand 'bf16x3' / 'bf16x6'"""
+    return _Bf16Math(prec) if prec == "bf16" else _SplitMath(prec)
 
 
 def _slot(p):
@@ -435,9 +475,9 @@ class _Block:
     def __init__(self, blk):
         self.fc1, self.fc2 = _Lin(blk.fc1, RELU), _Lin(blk.fc2, RELU)
 
-    def fwd(self, m, x):
+    def fwd(self, m, x, out=None):
         h = self.fc1.fwd(m, x)
-        return h, self.fc2.fwd(m, h, res=x)
+        return h, self.fc2.fwd(m, h, res=x, out=out)
 
     def bwd(self, m, gz2, h, x, x_act=RELU, out=None):
         """gz2: cotangent at fc2's pre-activation.  Returns (gz1, cotangent at the pre-activation of x's producer)."""
@@ -506,7 +546,7 @@ def _seeds(B, m, dev):
     s[:B] = -1.0 / B
     s[B:2 * B] = 1.0 / B
     s[2 * B:] = 1.0
-    return ops.cast_pad_bf16(s, 16) if m.bf16 else s
+    return m.seed_operand(s)
 
 
 _SEED_CACHE = {}
@@ -529,30 +569,52 @@ def _finish(optimizerD, logits, pen, pen_rows, lam, rows=None):
     return sc
 
 
-def step_d2(D, optimizerD, real, fake, alpha, lam, prec=None):
-    """Fk_2D_Discriminator (R/models_Fk_GAN/Fk_discriminator.py:236-266).  real, fake (B,32); alpha (B,1).
-    Returns the (5,) device tensor D_real, D_fake, GP, Wasserstein_D, D_cost; gradients are left in the optimizer's bucket
-    and the Adam step is taken."""
-    m = _Math(prec or D.precision)
-    L = [_Lin(D.pose_layer_1, LRELU, D.slope), _Lin(D.pose_layer_2, LRELU, D.slope), _Lin(D.pose_layer_3, LRELU, D.slope),
-         _Lin(D.pose_layer_4, NONE), _Lin(D.layer_last, LRELU, D.slope), _Lin(D.layer_pred, NONE)]
-    s = D.slope
-    optimizerD.zero_grad()
-    X = ops.gp_assemble(real, fake, alpha, bf16_rows=m.bf16 and SEED_CASTS)
-    B = X.shape[0] // 3
-    B2 = 2 * B
-    m.seed_cast(X[:B2], ceil16(X.shape[1]), getattr(X, "_dhaug_bf16_rows", None))
+def _partial_save(rows):
+    """may the forward-with-save launch of a step on `rows`-row parts skip some parts' block-layer images (SKIP_XHAT_SAVES)?"""
     from . import fused
-    if m.bf16 and FUSED_STEP_FORWARD and fused.step_forward_supported(D):
-        r = fused.critic2d_forward_save(D, X, save_rows=B2 if (SKIP_XHAT_SAVES and fused.partial_save_ok(B)) else 0)
-        (d1, d2, d3, d4, dl), logits = r["d"], r["logits"]
-    else:
+    return SKIP_XHAT_SAVES and fused.partial_save_ok(rows)
+
+
+class _D2Net:
+    """Fk_2D_Discriminator (R/models_Fk_GAN/Fk_discriminator.py:236-266) for both explicit steps: six layers, d3 = lrelu(L3 d2 + d1)"""
+
+    def __init__(self, D):
+        self.D, s = D, D.slope
+        self.L = [_Lin(D.pose_layer_1, LRELU, s), _Lin(D.pose_layer_2, LRELU, s), _Lin(D.pose_layer_3, LRELU, s),
+                  _Lin(D.pose_layer_4, NONE), _Lin(D.layer_last, LRELU, s), _Lin(D.layer_pred, NONE)]
+
+    def forward(self, m, X, save_rows):
+        """((d1, d2, d3, d4, dl), logits): one forward-with-save launch (fused.critic2d_forward_save, which writes the block
+        layers' images of rows [0, save_rows) only -- see SKIP_XHAT_SAVES) where it applies, layer by layer otherwise"""
+        from . import fused
+        if m.bf16 and FUSED_STEP_FORWARD and fused.step_forward_supported(self.D):
+            r = fused.critic2d_forward_save(self.D, X, save_rows=save_rows)
+            return r["d"], r["logits"]
+        L = self.L
         d1 = L[0].fwd(m, X)
         d2 = L[1].fwd(m, d1)
         d3 = L[2].fwd(m, d2, res=d1)
         d4 = L[3].fwd(m, d3)
         dl = L[4].fwd(m, d4)
-        logits = L[5].fwd(m, dl, out_f32=True)
+        return (d1, d2, d3, d4, dl), L[5].fwd(m, dl, out_f32=True)
+
+
+d2_net = _D2Net
+
+
+def step_d2(D, optimizerD, real, fake, alpha, lam, prec=None):
+    """Fk_2D_Discriminator.  real, fake (B,32); alpha (B,1).
+    Returns the (5,) device tensor D_real, D_fake, GP, Wasserstein_D, D_cost; gradients are left in the optimizer's bucket
+    and the Adam step is taken."""
+    m = math_for(prec or D.precision)
+    net = d2_net(D)
+    L, s = net.L, D.slope
+    optimizerD.zero_grad()
+    X = ops.gp_assemble(real, fake, alpha, bf16_rows=m.bf16 and SEED_CASTS)
+    B = X.shape[0] // 3
+    B2 = 2 * B
+    m.seed_cast(X[:B2], ceil16(X.shape[1]), getattr(X, "_dhaug_bf16_rows", None))
+    (d1, d2, d3, d4, dl), logits = net.forward(m, X, B2 if _partial_save(B) else 0)
     gzp = seeds(B, m, X.device)
     gzl = L[5].bwd(m, gzp, dl, LRELU, s)
     gz4 = L[4].bwd(m, gzl, d4, NONE, 0.0)
@@ -581,11 +643,10 @@ def step_d2(D, optimizerD, real, fake, alpha, lam, prec=None):
     u4 = L[3].tan(m, u3, tail(d4, B2), inplace=True)
     ul = L[4].tan(m, u4, tail(dl, B2), inplace=True)
     layers = ((L[0], gz1, X, v), (L[1], gz2, d1, u1), (L[2], gz3, d2, u2), (L[3], gz4, d3, u3), (L[4], gzl, d4, u4), (L[5], gzp, dl, ul))
-    if split:
-        for lay, gz, x, u in layers:
+    for lay, gz, x, u in layers:
+        if split:
             lay.grads_part(m, gz[B2:], u, False)
-    else:
-        for lay, gz, x, u in layers:
+        else:
             lay.grads(m, gz, x, B2, u, with_bias=not (lay is L[5] and m.bf16))
     m.flush()
     return _finish(optimizerD, logits, pen, B, lam)
@@ -599,7 +660,7 @@ class _Branch:
 
 
 def _layer_major(m, branches):
-    """wide branches of equal depth in bf16: their layers at the same depth run as one launch each (_Math.mm_group)"""
+    """wide branches of equal depth in bf16: their layers at the same depth run as one launch each (_Bf16Math.mm_group)"""
     return (m.bf16 and NT_GROUP and len(branches) > 1 and branches[0].first.N > 256
             and all(len(br.blocks) == len(branches[0].blocks) and br.first.N == branches[0].first.N for br in branches))
 
@@ -660,54 +721,71 @@ def _top_fusable(m, Lm, Mb, Lo, nb, Dw, M, masks, cat):
     return _top_shapes(m, Lm, Mb, Lo, nb, Dw) and ops.top_backward_ok(M, Lm.N, 512, masks, getattr(cat, "_dhaug_bits_cols", None))
 
 
-def step_branchnet(m, optimizerD, branches, Lm, Mb, Lo, X, rows, lam, feats, input_grad, tangents, pen_view=None, fwd=None, penalty=None):
-    """The four sweeps for a critic of the form  cat_b(branch_b(feat_b(x))) -> Linear(100)+ReLU -> myResNet(100) -> Linear(1).
-    X (3*rows, W) fp32 = [real; fake; x_hat] (ops.gp_assemble); feats(X) -> one fp32 input per branch (3*rows each);
-    input_grad([g_b]) -> dD/dx_hat (rows, W) fp32 from the branches' input cotangents (x_hat rows); tangents(v) -> one fp32
-    tangent input per branch (rows each).  pen_view: shape the penalty sees g in (default (rows, W); the 2D motion critic is
-    stepped with one interpolation coefficient per FRAME)."""
-    dev = X.device
-    B = rows
-    B2, M3 = 2 * B, 3 * B
-    nb, Dw = len(branches), branches[0].first.N
-    F = feats(X)
+class _BranchNet:
+    """A critic of the form  cat_b(branch_b(feat_b(x))) -> Linear(100)+ReLU -> myResNet(100) -> Linear(1), described once for
+    the critic step (3 * rows rows [real; fake; x_hat]) and the generator step (the fake rows alone):
+      feats(X) -> one fp32 input per branch, a row per row of X;
+      input_grad(x, gs) -> dD/dx (fp32, shaped like x) from the branches' input cotangents gs on the rows x of X;
+      tangents(x, v) -> one fp32 tangent input per branch for the tangent v at x;
+      pen_view: shape the penalty sees dD/dx_hat in (default: a row per row of x)."""
+
+    def __init__(self, branches, Lm, Mb, Lo, feats, input_grad, tangents, pen_view=None):
+        self.branches, self.Lm, self.Mb, self.Lo = branches, Lm, Mb, Lo
+        self.feats, self.input_grad, self.tangents, self.pen_view = feats, input_grad, tangents, pen_view
+        self.nb, self.Dw = len(branches), branches[0].first.N
+
+    def forward(self, m, F, layer_major=False):
+        """sweep 1 on the branch inputs F, every activation kept (the branch outputs land side by side: the concatenation is a
+        buffer, not a copy): dict(cat, y, h, m0, mh, m1, logits) with y[b] = [first layer, block outputs...], h[b] = the blocks'
+        hidden activations"""
+        Dw = self.Dw
+        cat = m.empty(F[0].shape[0], self.nb * Dw, F[0].device)
+        if layer_major:
+            y, h = _fwd_layer_major(m, self.branches, F, cat, Dw)
+        else:
+            y, h = [], []
+            for bi, br in enumerate(self.branches):
+                ys, hs = [br.first.fwd(m, F[bi])], []
+                for blk in br.blocks:
+                    hh, yy = blk.fwd(m, ys[-1], out=cat[:, bi * Dw:(bi + 1) * Dw] if blk is br.blocks[-1] else None)
+                    hs.append(hh); ys.append(yy)
+                y.append(ys); h.append(hs)
+        m0 = self.Lm.fwd(m, cat)
+        mh, m1 = self.Mb.fwd(m, m0)
+        return dict(cat=cat, y=y, h=h, m0=m0, mh=mh, m1=m1, logits=self.Lo.fwd(m, m1, out_f32=True))
+
+    def top_backward(self, m, seed, s):
+        """sweep 2 from the logit cotangent `seed` down to the concatenation, s = forward(): (gz_m2, gz_m1, gz_m0, gcat), the
+        cotangents at the merge block's fc2 / fc1, the merge layer and every branch's last fc2"""
+        Lm, Mb, Lo, nb, Dw = self.Lm, self.Mb, self.Lo, self.nb, self.Dw
+        cat, y, m0, mh, m1 = s["cat"], s["y"], s["m0"], s["mh"], s["m1"]
+        if Dw == 256 and all(getattr(y[bi][-1], "_dhaug_bits", None) is not None for bi in range(nb)):
+            cat._dhaug_bits_cols = [y[bi][-1]._dhaug_bits for bi in range(nb)]      # (the mask of column block bi: its branch's sign bits)
+        if _top_fusable(m, Lm, Mb, Lo, nb, Dw, cat.shape[0], (m1, mh, m0), cat):
+            # merge layer, merge block and logit layer in ONE launch: the 100-wide cotangents stay in LDS between the layers
+            return ops.critic_top_backward(
+                seed, A._w_nn(Lo.W, m.prec)[:, 0], m1, mh, m0, A._w_nn(Mb.fc2.W, m.prec), A._w_nn(Mb.fc1.W, m.prec), A._w_nn(Lm.W, m.prec),
+                cat._dhaug_bits_cols, Lm.N, RELU, 0.0)
+        gz_m2 = Lo.bwd(m, seed, m1, RELU, 0.0)
+        gz_m1, gz_m0 = Mb.bwd(m, gz_m2, mh, m0)
+        return gz_m2, gz_m1, gz_m0, Lm.bwd(m, gz_m0, cat, RELU, 0.0, out=m.empty_blocks(cat.shape[0], nb, Dw, cat.device))
+
+
+def step_branchnet(m, optimizerD, net, X, lam, F=None, fwd=None, penalty=None):
+    """The four sweeps for a _BranchNet critic.  X (3B, W) fp32 = [real; fake; x_hat] (ops.gp_assemble); F: net.feats(X)
+    where the caller has them already; fwd: sweep 1 as one fused launch that saves every layer's output (same buffers as
+    net.forward); penalty(gs, coef): sweep 3's head as one launch (bf16)."""
+    branches, Lm, Mb, Lo, nb, Dw = net.branches, net.Lm, net.Mb, net.Lo, net.nb, net.Dw
+    dev, B = X.device, X.shape[0] // 3
+    B2, xh = 2 * B, X[2 * B:]
+    F = net.feats(X) if F is None else F
     layer_major = _layer_major(m, branches)
-    # ---- 1. forward (the branch outputs land side by side: the concatenation is a buffer, not a copy)
-    if fwd is not None:                                      # one fused launch that saves every layer's output (same buffers)
-        r = fwd()
-        cat, y, h, m0, mh, m1, logits = r["cat"], r["y"], r["h"], r["m0"], r["mh"], r["m1"], r["logits"]
-    elif layer_major:
-        cat = m.empty(M3, nb * Dw, dev)
-        y, h = _fwd_layer_major(m, branches, F, cat, Dw)
-        m0 = Lm.fwd(m, cat)
-        mh, m1 = Mb.fwd(m, m0)
-        logits = Lo.fwd(m, m1, out_f32=True)
-    else:
-        cat = m.empty(M3, nb * Dw, dev)
-        y, h = [], []
-        for bi, br in enumerate(branches):
-            ys, hs = [br.first.fwd(m, F[bi])], []
-            for i, blk in enumerate(br.blocks):
-                hh = blk.fc1.fwd(m, ys[-1])
-                hs.append(hh)
-                ys.append(blk.fc2.fwd(m, hh, res=ys[-1], out=cat[:, bi * Dw:(bi + 1) * Dw] if i == len(br.blocks) - 1 else None))
-            y.append(ys); h.append(hs)
-        m0 = Lm.fwd(m, cat)
-        mh, m1 = Mb.fwd(m, m0)
-        logits = Lo.fwd(m, m1, out_f32=True)
+    # ---- 1. forward
+    r = fwd() if fwd is not None else net.forward(m, F, layer_major)
+    cat, y, h, m0, mh, m1, logits = r["cat"], r["y"], r["h"], r["m0"], r["mh"], r["m1"], r["logits"]
     # ---- 2. backward chain
     gzo = seeds(B, m, dev)
-    if Dw == 256 and all(getattr(y[bi][-1], "_dhaug_bits", None) is not None for bi in range(nb)):
-        cat._dhaug_bits_cols = [y[bi][-1]._dhaug_bits for bi in range(nb)]      # (the mask of column block bi: its branch's sign bits)
-    if _top_fusable(m, Lm, Mb, Lo, nb, Dw, M3, (m1, mh, m0), cat):
-        # merge layer, merge block and logit layer in ONE launch: the 100-wide cotangents stay in LDS between the layers
-        gz_m2, gz_m1, gz_m0, gcat = ops.critic_top_backward(
-            gzo, A._w_nn(Lo.W, m.prec)[:, 0], m1, mh, m0, A._w_nn(Mb.fc2.W, m.prec), A._w_nn(Mb.fc1.W, m.prec), A._w_nn(Lm.W, m.prec),
-            cat._dhaug_bits_cols, Lm.N, RELU, 0.0)
-    else:
-        gz_m2 = Lo.bwd(m, gzo, m1, RELU, 0.0)
-        gz_m1, gz_m0 = Mb.bwd(m, gz_m2, mh, m0)
-        gcat = Lm.bwd(m, gz_m0, cat, RELU, 0.0, out=m.empty_blocks(M3, nb, Dw, dev))   # (3B, nb*D): cotangents at every branch's last fc2
+    gz_m2, gz_m1, gz_m0, gcat = net.top_backward(m, gzo, r)
     g1, g2, gin = [], [], []
     if layer_major:
         g1, g2 = _bwd_layer_major(m, branches, gcat, h, y, Dw)
@@ -737,10 +815,10 @@ def step_branchnet(m, optimizerD, branches, Lm, Mb, Lo, X, rows, lam, feats, inp
         T, pen = penalty(gin, 2.0 * lam / B)
         n_pen = B
     else:
-        g = input_grad(gin)                                  # dD/dx_hat
-        gv = g if pen_view is None else g.reshape(pen_view)
+        g = net.input_grad(xh, gin)                                  # dD/dx_hat
+        gv = g if net.pen_view is None else g.reshape(net.pen_view)
         v, pen = ops.gp_penalty(gv, 2.0 * lam / gv.shape[0])
-        T = tangents(v.reshape(g.shape))
+        T = net.tangents(xh, v.reshape(g.shape))
         n_pen = gv.shape[0]
     u, uh = [], []
     if layer_major:
@@ -784,57 +862,45 @@ def step_branchnet(m, optimizerD, branches, Lm, Mb, Lo, X, rows, lam, feats, inp
     return _finish(optimizerD, logits, pen, n_pen, lam, rows=B)
 
 
-def step_d3(D, optimizerD, real, fake, alpha, lam, prec=None):
-    """Fk_3D_Discriminator (R/models_Fk_GAN/Fk_discriminator.py:149-201).  real, fake (B,16,3)|(B,48) root-relative."""
-    m = _Math(prec or D.precision)
-    br = [_Branch(D.special_KCS_previous[0], (D.special_KCS_block1, D.special_KCS_block2, D.special_KCS_block3)),
-          _Branch(D.previous[0], (D.block1, D.block2, D.block3))]
-    optimizerD.zero_grad()
-    X = ops.gp_assemble(real, fake, alpha, bf16_rows=m.bf16 and SEED_CASTS)  # (3B,48)
-    B = X.shape[0] // 3
-    xh = X[2 * B:]
+def _named_branches(D, names):
+    return [_Branch(getattr(D, n + "_previous")[0], [getattr(D, "%s_block%d" % (n, i)) for i in (1, 2, 3)]) for n in names]
+
+
+def d3_net(D):
+    """Fk_3D_Discriminator (R/models_Fk_GAN/Fk_discriminator.py:149-201) on root-relative poses (rows,48).  Branches: the KCS
+    features (d3_features) and the poses."""
+    return _BranchNet(
+        [_Branch(D.special_KCS_previous[0], (D.special_KCS_block1, D.special_KCS_block2, D.special_KCS_block3)),
+         _Branch(D.previous[0], (D.block1, D.block2, D.block3))],
+        _Lin(D.merge_previous[0], RELU), _Block(D.merge_block1), _Lin(D.output, NONE),
+        feats=None,                      # ([kf, X] with kf of d3_features: both steps hold it before they come here)
+        input_grad=lambda x, gs: ops.add_f32(ops.kcs_backward(x, gs[0], True), gs[1]),      # KCS^T path + pose path
+        tangents=lambda x, v: [ops.kcs_jvp(x, v, True), v])
+
+
+def d3_features(m, D, X, save_rows):
+    """(kf, kb, fwd): the 3D critic's fp32 KCS features of X and, where its forward-with-save launch applies (else None, None), their
+    bf16 operand and that launch (fused.critic3d_forward_save, which writes the block layers' images of rows [0, save_rows) only)"""
     from . import fused
     use = m.bf16 and FUSED_STEP_FORWARD and fused.step_forward_supported(D)
-    kf, kb = ops.kcs_forward(X, True, f32=True, bf16_ld=32 if use else 0)    # fp32 features (first layer's weight gradient) [+ bf16 operand]
-    if SEED_CASTS:                                                           # sweep 4's bf16 operands of the two input layers exist already
-        m.seed_cast(X[:2 * B], ceil16(X.shape[1]), getattr(X, "_dhaug_bf16_rows", None))
-        if use and kb is not None:
-            m.seed_cast(kf[:2 * B], 32, kb[:2 * B])
-    sr = 2 * B if (use and SKIP_XHAT_SAVES and fused.partial_save_ok(B)) else 0
-    return step_branchnet(
-        m, optimizerD, br, _Lin(D.merge_previous[0], RELU), _Block(D.merge_block1), _Lin(D.output, NONE), X, B, lam,
-        feats=lambda X: [kf, X],
-        input_grad=lambda gs: ops.add_f32(ops.kcs_backward(xh, gs[0], True), gs[1]),      # KCS^T path + pose path
-        tangents=lambda v: [ops.kcs_jvp(xh, v, True), v],
-        fwd=(lambda: fused.critic3d_forward_save(D, X, kb, save_rows=sr)) if use else None,
-        penalty=(lambda gs, coef: (lambda r: ([r[0], r[1]], r[2]))(ops.d3_penalty(xh, gs[0], gs[1], coef))) if D3_PENALTY_FUSED else None)
+    kf, kb = ops.kcs_forward(X, True, f32=True, bf16_ld=32 if use else 0)
+    return kf, kb, (lambda: fused.critic3d_forward_save(D, X, kb, save_rows=save_rows)) if use else None
 
 
-def step_m3(D, optimizerD, real, fake, alpha, lam, prec=None):
-    """Video_motion_Fk_3D_Discriminator (R/models_Fk_GAN/Fk_discriminator.py:381-512), stepped with dis_mode='motion':
-    real, fake (B, R*48) clips, alpha (B,1), penalty over the B clips.  Branches: per-frame KCS cosines (R*15), their frame
-    differences ((R-1)*15), the poses (R*48), their frame differences ((R-1)*48)."""
-    m = _Math(prec or D.precision)
+def m3_net(D):
+    """Video_motion_Fk_3D_Discriminator (R/models_Fk_GAN/Fk_discriminator.py:381-512) on clips (rows, R*48).  Branches: per-frame
+    KCS cosines (R*15), their frame differences ((R-1)*15), the poses (R*48), their frame differences ((R-1)*48)."""
     R = D.video_frame_num
-    names = ["special_KCS", "diff_special_KCS"] + (["pos_3d"] if D.use_pos else []) + (["diff_pos_3d"] if D.use_diff else [])
-    br = [_Branch(getattr(D, n + "_previous")[0], [getattr(D, "%s_block%d" % (n, i)) for i in (1, 2, 3)]) for n in names]
-    optimizerD.zero_grad()
-    X = ops.gp_assemble(real, fake, alpha)                                   # (3B, R*48)
-    B = X.shape[0] // 3
-    xh = X[2 * B:].reshape(B * R, 48)
+    # the pose branches of a clip-shaped tensor, in the order of the critic's branches
+    pose = lambda t: ([t] if D.use_pos else []) + ([ops.frame_diff(t, R, 48)] if D.use_diff else [])
 
     def feats(X):
         kc = ops.kcs_forward(X.reshape(-1, 48), False, f32=True)[0].reshape(-1, R * 15)
-        out = [kc, ops.frame_diff(kc, R, 15)]
-        if D.use_pos:
-            out.append(X)
-        if D.use_diff:
-            out.append(ops.frame_diff(X, R, 48))
-        return out
+        return [kc, ops.frame_diff(kc, R, 15)] + pose(X)
 
-    def input_grad(gs):
+    def input_grad(x, gs):
         gk = ops.add_f32(gs[0], ops.frame_diff(gs[1], R, 15, adjoint=True))   # cotangent of the per-frame cosines
-        g = ops.kcs_backward(xh, gk.reshape(B * R, 15), False).reshape(B, R * 48)
+        g = ops.kcs_backward(x.reshape(-1, 48), gk.reshape(-1, 15), False).reshape(-1, R * 48)
         i = 2
         if D.use_pos:
             g = ops.add_f32(g, gs[i]); i += 1
@@ -842,38 +908,61 @@ def step_m3(D, optimizerD, real, fake, alpha, lam, prec=None):
             g = ops.add_f32(g, ops.frame_diff(gs[i], R, 48, adjoint=True))
         return g
 
-    def tangents(v):
-        tk = ops.kcs_jvp(xh, v.reshape(B * R, 48), False).reshape(B, R * 15)
-        out = [tk, ops.frame_diff(tk, R, 15)]
-        if D.use_pos:
-            out.append(v)
-        if D.use_diff:
-            out.append(ops.frame_diff(v, R, 48))
-        return out
+    def tangents(x, v):
+        tk = ops.kcs_jvp(x.reshape(-1, 48), v.reshape(-1, 48), False).reshape(-1, R * 15)
+        return [tk, ops.frame_diff(tk, R, 15)] + pose(v)
 
-    return step_branchnet(m, optimizerD, br, _Lin(D.kcs_merge_previous[0], RELU), _Block(D.kcs_merge_block1),
-                          _Lin(D.kcs_output, NONE), X, B, lam, feats, input_grad, tangents)
+    names = ["special_KCS", "diff_special_KCS"] + (["pos_3d"] if D.use_pos else []) + (["diff_pos_3d"] if D.use_diff else [])
+    return _BranchNet(_named_branches(D, names), _Lin(D.kcs_merge_previous[0], RELU), _Block(D.kcs_merge_block1),
+                      _Lin(D.kcs_output, NONE), feats, input_grad, tangents)
+
+
+def m2_net(D):
+    """Video_motion_Fk_2D_Discriminator (R/models_Fk_GAN/Fk_discriminator.py:516-587) on clips (rows, R*32).  Branches: the
+    clip's 2D poses (R*32) and the frame differences of its root joint ((R-1)*2).  The penalty is taken per FRAME."""
+    R = D.video_frame_num
+    return _BranchNet(
+        _named_branches(D, ("pos_2d", "root_diff_2d")), _Lin(D.merge_previous[0], RELU), _Block(D.merge_block1), _Lin(D.merge_output, NONE),
+        feats=lambda X: [X, ops.frame_diff(X, R, 32, 2)],
+        input_grad=lambda x, gs: ops.add_f32(gs[0], ops.frame_diff(gs[1], R, 32, 2, adjoint=True)),
+        tangents=lambda x, v: [v, ops.frame_diff(v, R, 32, 2)],
+        pen_view=(-1, 32))
+
+
+def step_d3(D, optimizerD, real, fake, alpha, lam, prec=None):
+    """Fk_3D_Discriminator.  real, fake (B,16,3)|(B,48) root-relative."""
+    m = math_for(prec or D.precision)
+    optimizerD.zero_grad()
+    X = ops.gp_assemble(real, fake, alpha, bf16_rows=m.bf16 and SEED_CASTS)  # (3B,48)
+    B = X.shape[0] // 3
+    kf, kb, fwd = d3_features(m, D, X, 2 * B if _partial_save(B) else 0)    # fp32 features (first layer's weight gradient) [+ bf16 operand]
+    if SEED_CASTS:                                                           # sweep 4's bf16 operands of the two input layers exist already
+        m.seed_cast(X[:2 * B], ceil16(X.shape[1]), getattr(X, "_dhaug_bf16_rows", None))
+        if fwd is not None and kb is not None:
+            m.seed_cast(kf[:2 * B], 32, kb[:2 * B])
+    xh = X[2 * B:]
+    return step_branchnet(
+        m, optimizerD, d3_net(D), X, lam, F=[kf, X], fwd=fwd,
+        penalty=(lambda gs, coef: (lambda r: ([r[0], r[1]], r[2]))(ops.d3_penalty(xh, gs[0], gs[1], coef))) if D3_PENALTY_FUSED else None)
+
+
+def step_m3(D, optimizerD, real, fake, alpha, lam, prec=None):
+    """Video_motion_Fk_3D_Discriminator, stepped with dis_mode='motion': real, fake (B, R*48) clips, alpha (B,1), penalty over
+    the B clips."""
+    m = math_for(prec or D.precision)
+    optimizerD.zero_grad()
+    return step_branchnet(m, optimizerD, m3_net(D), ops.gp_assemble(real, fake, alpha), lam)       # (3B, R*48)
 
 
 def step_m2(D, optimizerD, real, fake, alpha, lam, prec=None):
-    """Video_motion_Fk_2D_Discriminator (R/models_Fk_GAN/Fk_discriminator.py:516-587) as the video loop steps it: the DEFAULT
-    mode of train_Fk_discriminator, i.e. real, fake (B*R, 32) frames, alpha (B*R, 1) -- one interpolation coefficient per
-    frame -- and the penalty over the B*R per-frame gradient norms (R/models_Fk_GAN/video_GAN_fun.py:341-346).  Branches: the
-    clip's 2D poses (R*32) and the frame differences of its root joint ((R-1)*2)."""
-    m = _Math(prec or D.precision)
-    R = D.video_frame_num
-    br = [_Branch(getattr(D, n + "_previous")[0], [getattr(D, "%s_block%d" % (n, i)) for i in (1, 2, 3)])
-          for n in ("pos_2d", "root_diff_2d")]
+    """Video_motion_Fk_2D_Discriminator as the video loop steps it: the DEFAULT mode of train_Fk_discriminator, i.e. real,
+    fake (B*R, 32) frames, alpha (B*R, 1) -- one interpolation coefficient per frame -- and the penalty over the B*R
+    per-frame gradient norms (R/models_Fk_GAN/video_GAN_fun.py:341-346)."""
+    m = math_for(prec or D.precision)
     optimizerD.zero_grad()
     Xf = ops.gp_assemble(real, fake, alpha)                                  # (3*B*R, 32): interpolated per frame
-    B = Xf.shape[0] // (3 * R)
-    X = Xf.reshape(3 * B, R * 32)                                            # clips (real, fake and interpolated frames stay together)
-    return step_branchnet(
-        m, optimizerD, br, _Lin(D.merge_previous[0], RELU), _Block(D.merge_block1), _Lin(D.merge_output, NONE), X, B, lam,
-        feats=lambda X: [X, ops.frame_diff(X, R, 32, 2)],
-        input_grad=lambda gs: ops.add_f32(gs[0], ops.frame_diff(gs[1], R, 32, 2, adjoint=True)),
-        tangents=lambda v: [v, ops.frame_diff(v, R, 32, 2)],
-        pen_view=(B * R, 32))
+    # clips (3B, R*32): real, fake and interpolated frames stay together
+    return step_branchnet(m, optimizerD, m2_net(D), Xf.reshape(-1, D.video_frame_num * 32), lam)
 
 
 def supported(model_dis, optimizerD, real, fake, rows):

@@ -19,98 +19,37 @@ from . import critic_step as CS
 from . import ops
 
 NONE, RELU, LRELU = A.ACT_NONE, A.ACT_RELU, A.ACT_LRELU
-BF16 = torch.bfloat16
 
 
 def _const_seed(rows, value, m, dev):
-    s = torch.full((rows, 1), float(value), dtype=torch.float32, device=dev)
-    return ops.cast_pad_bf16(s, 16) if m.bf16 else s
+    return m.seed_operand(torch.full((rows, 1), float(value), dtype=torch.float32, device=dev))
 
 
-class _BranchNet:
-    """cat_b(branch_b(feat_b(x))) -> Linear(100)+ReLU -> myResNet(100) -> Linear(1): forward keeping every activation, and
-    the input-gradient chain of a constant logit cotangent (weights frozen: no weight gradients)."""
-
-    def __init__(self, branches, Lm, Mb, Lo):
-        self.br, self.Lm, self.Mb, self.Lo = branches, Lm, Mb, Lo
-
-    def forward(self, m, F, fwd=None):
-        if fwd is not None:
-            return fwd()
-        rows, dev = F[0].shape[0], F[0].device
-        nb, Dw = len(self.br), self.br[0].first.N
-        cat = m.empty(rows, nb * Dw, dev)
-        y, h = [], []
-        for bi, br in enumerate(self.br):
-            ys, hs = [br.first.fwd(m, F[bi])], []
-            for i, blk in enumerate(br.blocks):
-                hh = blk.fc1.fwd(m, ys[-1])
-                hs.append(hh)
-                ys.append(blk.fc2.fwd(m, hh, res=ys[-1], out=cat[:, bi * Dw:(bi + 1) * Dw] if i == len(br.blocks) - 1 else None))
-            y.append(ys); h.append(hs)
-        m0 = self.Lm.fwd(m, cat)
-        mh, m1 = self.Mb.fwd(m, m0)
-        logits = self.Lo.fwd(m, m1, out_f32=True)
-        return dict(cat=cat, y=y, h=h, m0=m0, mh=mh, m1=m1, logits=logits)
-
-    def input_grads(self, m, s, seed):
-        """s: forward(); seed (rows,1) logit cotangent -> one fp32 input cotangent per branch"""
-        Dw = self.br[0].first.N
-        cat = s["cat"]
-        if Dw == 256 and all(getattr(s["y"][bi][-1], "_dhaug_bits", None) is not None for bi in range(len(self.br))):
-            cat._dhaug_bits_cols = [s["y"][bi][-1]._dhaug_bits for bi in range(len(self.br))]
-        if CS._top_fusable(m, self.Lm, self.Mb, self.Lo, len(self.br), Dw, cat.shape[0], (s["m1"], s["mh"], s["m0"]), cat):
-            # (merge layer, merge block and logit layer in one launch, as in the critic step: ops.critic_top_backward)
-            _, _, _, gcat = ops.critic_top_backward(
-                seed, CS.A._w_nn(self.Lo.W, m.prec)[:, 0], s["m1"], s["mh"], s["m0"], CS.A._w_nn(self.Mb.fc2.W, m.prec),
-                CS.A._w_nn(self.Mb.fc1.W, m.prec), CS.A._w_nn(self.Lm.W, m.prec), cat._dhaug_bits_cols, self.Lm.N, RELU, 0.0)
-        else:
-            gz_m2 = self.Lo.bwd(m, seed, s["m1"], RELU, 0.0)
-            _, gz_m0 = self.Mb.bwd(m, gz_m2, s["mh"], s["m0"])
-            gcat = self.Lm.bwd(m, gz_m0, cat, RELU, 0.0, out=m.empty_blocks(cat.shape[0], len(self.br), Dw, cat.device))
-        gin = []
-        for bi, br in enumerate(self.br):
-            _, a2 = CS.stack_bwd(m, br.blocks, gcat[:, bi * Dw:(bi + 1) * Dw], s["h"][bi], s["y"][bi])
-            gin.append(br.first.bwd(m, a2[0], None, NONE, 0.0, out_f32=True))
-        return gin
-
-
-def _d3_net(D):
-    return _BranchNet([CS._Branch(D.special_KCS_previous[0], (D.special_KCS_block1, D.special_KCS_block2, D.special_KCS_block3)),
-                       CS._Branch(D.previous[0], (D.block1, D.block2, D.block3))],
-                      CS._Lin(D.merge_previous[0], RELU), CS._Block(D.merge_block1), CS._Lin(D.output, NONE))
+def _branch_value_grad(m, net, X, coef, F=None, fwd=None):
+    """X (rows, W) fakes as the critic net (critic_step._BranchNet) takes them -> (logits (rows,1), coef * d mean D / d X fp32):
+    forward keeping every activation, then the input-gradient chain of the constant logit cotangent coef / rows -- critic_step's
+    sweep 2, branch by branch, on all rows (weights frozen: no weight gradients)."""
+    rows, Dw = X.shape[0], net.Dw
+    s = fwd() if fwd is not None else net.forward(m, net.feats(X) if F is None else F)
+    gcat = net.top_backward(m, _const_seed(rows, coef / rows, m, X.device), s)[3]
+    gin = []
+    for bi, br in enumerate(net.branches):
+        _, a2 = CS.stack_bwd(m, br.blocks, gcat[:, bi * Dw:(bi + 1) * Dw], s["h"][bi], s["y"][bi])
+        gin.append(br.first.bwd(m, a2[0], None, NONE, 0.0, out_f32=True))
+    return s["logits"], net.input_grad(X, gin)
 
 
 def _d3_value_grad(m, D, fc, coef):
     """fc (N,48) root-relative fakes -> (logits (N,1), coef * d mean D3 / d fc  (N,48) fp32)"""
-    from . import fused
-    net = _d3_net(D)
-    N = fc.shape[0]
-    use = m.bf16 and CS.FUSED_STEP_FORWARD and fused.step_forward_supported(D)
-    kf, kb = ops.kcs_forward(fc, True, f32=True, bf16_ld=32 if use else 0)
-    sr = -1 if (CS.SKIP_XHAT_SAVES and fused.partial_save_ok(N)) else 0          # (only masks are read back: the block layers leave their sign bits)
-    s = net.forward(m, [kf, fc], fwd=(lambda: fused.critic3d_forward_save(D, fc, kb, save_rows=sr)) if use else None)
-    gk, gp = net.input_grads(m, s, _const_seed(N, coef / N, m, fc.device))
-    return s["logits"], ops.add_f32(ops.kcs_backward(fc, gk, True), gp)
+    kf, _, fwd = CS.d3_features(m, D, fc, -1 if CS._partial_save(fc.shape[0]) else 0)    # (-1: only masks are read back, the blocks' sign bits)
+    return _branch_value_grad(m, CS.d3_net(D), fc, coef, F=[kf, fc], fwd=fwd)
 
 
 def _d2_value_grad(m, D, x, coef):
-    """x (N,32) projections -> (logits, coef * d mean D2 / d x (N,32) fp32).  R/models_Fk_GAN/Fk_discriminator.py:253-266"""
-    from . import fused
-    sl = D.slope
-    L = [CS._Lin(D.pose_layer_1, LRELU, sl), CS._Lin(D.pose_layer_2, LRELU, sl), CS._Lin(D.pose_layer_3, LRELU, sl),
-         CS._Lin(D.pose_layer_4, NONE), CS._Lin(D.layer_last, LRELU, sl), CS._Lin(D.layer_pred, NONE)]
-    N = x.shape[0]
-    if m.bf16 and CS.FUSED_STEP_FORWARD and fused.step_forward_supported(D):
-        r = fused.critic2d_forward_save(D, x, save_rows=-1 if (CS.SKIP_XHAT_SAVES and fused.partial_save_ok(N)) else 0)
-        (d1, d2, d3, d4, dl), logits = r["d"], r["logits"]
-    else:
-        d1 = L[0].fwd(m, x)
-        d2 = L[1].fwd(m, d1)
-        d3 = L[2].fwd(m, d2, res=d1)
-        d4 = L[3].fwd(m, d3)
-        dl = L[4].fwd(m, d4)
-        logits = L[5].fwd(m, dl, out_f32=True)
+    """x (N,32) projections -> (logits, coef * d mean D2 / d x (N,32) fp32)"""
+    net = CS.d2_net(D)
+    L, sl, N = net.L, D.slope, x.shape[0]
+    (d1, d2, d3, d4, dl), logits = net.forward(m, x, -1 if CS._partial_save(N) else 0)
     gzl = L[5].bwd(m, _const_seed(N, coef / N, m, x.device), dl, LRELU, sl)
     gz4 = L[4].bwd(m, gzl, d4, NONE, 0.0)
     gz3 = L[3].bwd(m, gz4, d3, LRELU, sl)
@@ -119,45 +58,10 @@ def _d2_value_grad(m, D, x, coef):
     return logits, L[0].bwd(m, gz1, None, NONE, 0.0, out_f32=True)
 
 
-def _m3_value_grad(m, D, fc, coef):
-    """3D motion critic on clips: fc (B*R,48) -> (logits (B,1), coef * d mean / d fc (B*R,48)).  Branch features as in
-    critic_step.step_m3 (R/models_Fk_GAN/Fk_discriminator.py:381-512)."""
-    R = D.video_frame_num
-    names = ["special_KCS", "diff_special_KCS"] + (["pos_3d"] if D.use_pos else []) + (["diff_pos_3d"] if D.use_diff else [])
-    net = _BranchNet([CS._Branch(getattr(D, n + "_previous")[0], [getattr(D, "%s_block%d" % (n, i)) for i in (1, 2, 3)]) for n in names],
-                     CS._Lin(D.kcs_merge_previous[0], RELU), CS._Block(D.kcs_merge_block1), CS._Lin(D.kcs_output, NONE))
-    X = fc.reshape(-1, R * 48)
-    B = X.shape[0]
-    kc = ops.kcs_forward(fc.reshape(-1, 48), False, f32=True)[0].reshape(B, R * 15)
-    F = [kc, ops.frame_diff(kc, R, 15)]
-    if D.use_pos:
-        F.append(X)
-    if D.use_diff:
-        F.append(ops.frame_diff(X, R, 48))
-    s = net.forward(m, F)
-    gs = net.input_grads(m, s, _const_seed(B, coef / B, m, fc.device))
-    gk = ops.add_f32(gs[0], ops.frame_diff(gs[1], R, 15, adjoint=True))
-    g = ops.kcs_backward(fc.reshape(-1, 48), gk.reshape(B * R, 15), False).reshape(B, R * 48)
-    i = 2
-    if D.use_pos:
-        g = ops.add_f32(g, gs[i]); i += 1
-    if D.use_diff:
-        g = ops.add_f32(g, ops.frame_diff(gs[i], R, 48, adjoint=True))
-    return s["logits"], g.reshape(B * R, 48)
-
-
-def _m2_value_grad(m, D, x, coef):
-    """2D motion critic: x (B*R,32) -> (logits (B,1), coef * d mean / d x (B*R,32)).  R/models_Fk_GAN/Fk_discriminator.py:516-587"""
-    R = D.video_frame_num
-    net = _BranchNet([CS._Branch(getattr(D, n + "_previous")[0], [getattr(D, "%s_block%d" % (n, i)) for i in (1, 2, 3)])
-                      for n in ("pos_2d", "root_diff_2d")],
-                     CS._Lin(D.merge_previous[0], RELU), CS._Block(D.merge_block1), CS._Lin(D.merge_output, NONE))
-    X = x.reshape(-1, R * 32)
-    B = X.shape[0]
-    s = net.forward(m, [X, ops.frame_diff(X, R, 32, 2)])
-    gs = net.input_grads(m, s, _const_seed(B, coef / B, m, x.device))
-    g = ops.add_f32(gs[0], ops.frame_diff(gs[1], R, 32, 2, adjoint=True))
-    return s["logits"], g.reshape(B * R, 32)
+def _motion_value_grad(m, D, net, x, coef):
+    """a motion critic D (net: critic_step.m3_net / m2_net) on clips: x (B*R, w) frames -> (logits (B,1), coef * d mean / d x (B*R, w))"""
+    l, g = _branch_value_grad(m, net(D), x.reshape(-1, D.video_frame_num * x.shape[1]), coef)
+    return l, g.reshape(x.shape)
 
 
 CONCURRENT = __import__("os").environ.get("DHAUG_NO_CONCURRENT_CRITICS") is None
@@ -238,7 +142,7 @@ def generator_step(args, G, oG, critics, weights, camera, flip, noise, scaler, f
     dev = noise.device
     quat, trans, cam9 = camera
     R = frames
-    mG = CS._Math(graph_precision(G.precision))
+    mG = CS.math_for(graph_precision(G.precision))
     oG.zero_grad()
     # ---- forward: trunk (every activation kept), FK tail, camera
     Lp = CS._Lin(G.preprocess[0], RELU)
@@ -265,29 +169,29 @@ def generator_step(args, G, oG, critics, weights, camera, flip, noise, scaler, f
     x2 = f2d.reshape(N, 32)
     # ---- critics: value + input gradient of -w * mean D(.) (the L/R-flipped copies halve the weight of the plain ones)
     half = 0.5 if flip else 1.0
-    m3d, m2d = CS._Math(graph_precision(critics[0].precision)), CS._Math(graph_precision(critics[1].precision))
+    m3d, m2d = CS.math_for(graph_precision(critics[0].precision)), CS.math_for(graph_precision(critics[1].precision))
     jobs = [lambda: _d3_value_grad(m3d, critics[0], fc, -weights[0] * half),
             lambda: _d2_value_grad(m2d, critics[1], x2, -weights[1] * half)]
     wts = [weights[0] * half, weights[1] * half]
     kinds = ["fc", "x2"]
     rev = lambda t: ops.frame_reverse(t.reshape(-1, R * 32), R, 32)
     if len(critics) == 4:
-        mm3, mm2 = CS._Math(graph_precision(critics[2].precision)), CS._Math(graph_precision(critics[3].precision))
+        mm3, mm2 = CS.math_for(graph_precision(critics[2].precision)), CS.math_for(graph_precision(critics[3].precision))
         ph = 0.5 if playback else 1.0
-        jobs += [lambda: _m3_value_grad(mm3, critics[2], fc, -weights[2] * half * ph),
-                 lambda: _m2_value_grad(mm2, critics[3], x2, -weights[3] * half * ph)]
+        jobs += [lambda: _motion_value_grad(mm3, critics[2], CS.m3_net, fc, -weights[2] * half * ph),
+                 lambda: _motion_value_grad(mm2, critics[3], CS.m2_net, x2, -weights[3] * half * ph)]
         wts += [weights[2] * half * ph, weights[3] * half * ph]
         kinds += ["fc", "x2"]
         if playback:
             # the reference reverses the frames of the clip VIEWED as (-1, R, 32) -- also for the 3D clip: a
             # permutation of the clip's values that is its own transpose
             def rev3_job():
-                l, g = _m3_value_grad(CS._Math(graph_precision(critics[2].precision)), critics[2], rev(fc).reshape(N, 48),
+                l, g = _motion_value_grad(CS.math_for(graph_precision(critics[2].precision)), critics[2], CS.m3_net, rev(fc).reshape(N, 48),
                                       -weights[2] * half * ph)
                 return l, rev(g).reshape(N, 48)
 
             def rev2_job():
-                l, g = _m2_value_grad(CS._Math(graph_precision(critics[3].precision)), critics[3], rev(x2).reshape(N, 32),
+                l, g = _motion_value_grad(CS.math_for(graph_precision(critics[3].precision)), critics[3], CS.m2_net, rev(x2).reshape(N, 32),
                                       -weights[3] * half * ph)
                 return l, rev(g).reshape(N, 32)
             jobs += [rev3_job, rev2_job]

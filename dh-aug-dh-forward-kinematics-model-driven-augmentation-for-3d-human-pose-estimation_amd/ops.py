@@ -1,5 +1,6 @@
 """Tensor-level wrappers of the C-ABI (no autograd here): allocate outputs with torch, pass raw device pointers and
 the current HIP stream to libdhaug.so.  Every function requires CUDA(HIP) tensors and raises otherwise."""
+import collections
 import ctypes
 import os
 
@@ -838,16 +839,21 @@ def tn_group_ok(M, N1, N2, colsum_rows):
 TN_WIDE_MIN_BLOCKS = int(os.environ.get("DHAUG_TN_WIDE_MIN_BLOCKS", "128"))
 
 
+# one weight gradient of gemm_tn_group: out[N1,N2] (+)= A[M,N1]^T B[M,N2], colsum[N1] (+)= column sums of A over rows [0, colsum_rows);
+# M, lda, ldb default to A's rows and the operands' row pitches; planes_a / planes_b: A / B as the three planes of a split operand (dhaug_tn_layer)
+TnItem = collections.namedtuple("TnItem", "A B N1 N2 out colsum colsum_rows accumulate M lda ldb planes_a planes_b",
+                                defaults=(None, 0, True, None, None, None, 0, 0))
+
+
 def gemm_tn_group(items, max_workgroups=0):
-    """items: [(A, B, N1, N2, out, colsum | None, colsum_rows, accumulate, M | None, lda | None, ldb | None)] -- the weight
-    gradients C_i (+)= A_i^T B_i of several layers in one launch (+ one that sums the partial results).
+    """items: TnItems (or plain tuples of their leading fields) -- the weight gradients C_i (+)= A_i^T B_i of several layers in
+    one launch (+ one that sums the partial results).
     max_workgroups: leave CUs to kernels running beside this launch (0: one workgroup per CU)."""
     # layers wider than 256: whole ("wide": one workgroup per 256 x 256 block, which adds into the gradient slot itself) where the
     # chunk they travel in has blocks enough to fill the card without splitting any over the batch; as 256 x 256 blocks, each an
     # item of its own, otherwise (a long batch of few wide layers: the blocks are split over the batch and summed)
-    nblk = lambda it: ((it[2] + 255) // 256) * ((it[3] + 255) // 256)
-    # items may carry two more fields, (planes_a, planes_b): A / B as the three planes of a split operand (dhaug_tn_layer.planes_a / _b)
-    items = [tuple(it) if len(it) == 13 else tuple(it) + (0, 0) for it in items]
+    nblk = lambda it: ((it.N1 + 255) // 256) * ((it.N2 + 255) // 256)
+    items = [it if type(it) is TnItem else TnItem(*it) for it in items]
     if any(nblk(it) > 1 for it in items):
         flat = []
         for i0 in range(0, len(items), _lib.TN_GROUP_MAX):
@@ -855,21 +861,21 @@ def gemm_tn_group(items, max_workgroups=0):
             if sum(nblk(it) for it in chunk) >= TN_WIDE_MIN_BLOCKS:
                 flat.extend(chunk)
                 continue
-            for (A, B, N1, N2, out, cs, cr, accumulate, M, la, lb, pa, pb) in chunk:
-                assert (pa == 0 and pb == 0) or (N1 <= 256 and N2 <= 256), "a wide layer's operands as planes: not built"
-                for n0 in range(0, N1, 256):
-                    for k0 in range(0, N2, 256):
-                        c = cs[n0:] if (cs is not None and k0 == 0) else None
-                        flat.append((A[:, n0:], B[:, k0:], min(256, N1 - n0), min(256, N2 - k0), out[n0:, k0:], c,
-                                     cr if c is not None else 0, accumulate, A.shape[0] if M is None else M, la, lb, pa, pb))
+            for it in chunk:
+                assert (it.planes_a == 0 and it.planes_b == 0) or (it.N1 <= 256 and it.N2 <= 256), "a wide layer's operands as planes: not built"
+                for n0 in range(0, it.N1, 256):
+                    for k0 in range(0, it.N2, 256):
+                        c = it.colsum[n0:] if (it.colsum is not None and k0 == 0) else None
+                        flat.append(it._replace(A=it.A[:, n0:], B=it.B[:, k0:], N1=min(256, it.N1 - n0), N2=min(256, it.N2 - k0),
+                                                out=it.out[n0:, k0:], colsum=c, colsum_rows=it.colsum_rows if c is not None else 0,
+                                                M=it.A.shape[0] if it.M is None else it.M))
         items = flat
     # the items of ONE launch are summed into their outputs concurrently (a block that is left with one workgroup adds its
     # result into C / colsum with a plain read-modify-write): two items with the same output must not share a launch
     # (include/dhaug.h, dhaug_gemm_tn_group_bf16).  A later contribution to an output waits for a launch of its own.
-    seen, later = set(), []
-    first = []
+    seen, first, later = set(), [], []
     for it in items:
-        keys = {("C", _p(it[4]))} | ({("s", _p(it[5]))} if it[5] is not None else set())
+        keys = {("C", _p(it.out))} | ({("s", _p(it.colsum))} if it.colsum is not None else set())
         if keys & seen:
             later.append(it)
         else:
@@ -882,14 +888,15 @@ def gemm_tn_group(items, max_workgroups=0):
     for i0 in range(0, len(items), _lib.TN_GROUP_MAX):
         chunk = items[i0:i0 + _lib.TN_GROUP_MAX]
         arr = (_lib.TnLayer * len(chunk))()
-        for d, (A, B, N1, N2, out, cs, cr, accumulate, M, la, lb, pa, pb) in zip(arr, chunk):
-            d.planes_a, d.planes_b = int(pa), int(pb)
+        for d, it in zip(arr, chunk):
+            A, B, out = it.A, it.B, it.out
             assert A.dtype == BF16 and B.dtype == BF16 and out.dtype == torch.float32
-            d.A, d.lda, d.B, d.ldb = _p(A), A.stride(0) if la is None else la, _p(B), B.stride(0) if lb is None else lb
-            d.C, d.ldc, d.colsum_a, d.colsum_rows = _p(out), out.stride(0), _p(cs), cr
-            d.M, d.N1, d.N2, d.accumulate = A.shape[0] if M is None else M, N1, N2, int(bool(accumulate))
+            d.planes_a, d.planes_b = int(it.planes_a), int(it.planes_b)
+            d.A, d.lda, d.B, d.ldb = _p(A), A.stride(0) if it.lda is None else it.lda, _p(B), B.stride(0) if it.ldb is None else it.ldb
+            d.C, d.ldc, d.colsum_a, d.colsum_rows = _p(out), out.stride(0), _p(it.colsum), it.colsum_rows
+            d.M, d.N1, d.N2, d.accumulate = A.shape[0] if it.M is None else it.M, it.N1, it.N2, int(bool(it.accumulate))
             d.max_workgroups = int(max_workgroups)
-        _lib.call("dhaug_gemm_tn_group_bf16", arr, len(chunk), _p(_tn_group_workspace(chunk[0][0].device)), _stream())
+        _lib.call("dhaug_gemm_tn_group_bf16", arr, len(chunk), _p(_tn_group_workspace(chunk[0].A.device)), _stream())
 
 
 def gemm_tn(A, B, N1, N2, out=None, accumulate=False, M=None, lda=None, ldb=None, colsum=None, colsum_rows=None):
@@ -904,10 +911,9 @@ def gemm_tn(A, B, N1, N2, out=None, accumulate=False, M=None, lda=None, ldb=None
     cr = M if colsum_rows is None else colsum_rows
     if TN256 and N1 == 256 and N2 == 256 and tn_group_ok(M, N1, N2, cr):
         # a long 256 x 256 contraction alone: a group of one (whole-output tiles, dhaug_tn256.hip)
-        gemm_tn_group([(A, B, N1, N2, out, colsum, cr, accumulate, M, la, lb)])
+        gemm_tn_group([TnItem(A=A, B=B, N1=N1, N2=N2, out=out, colsum=colsum, colsum_rows=cr, accumulate=accumulate, M=M, lda=la, ldb=lb)])
         return out
-    _lib.call("dhaug_gemm_tn_bf16_rows", _p(A), A.stride(0) if lda is None else lda, _p(B), B.stride(0) if ldb is None else ldb,
-              _p(out), out.stride(0), _p(colsum), M if colsum_rows is None else colsum_rows, M, N1, N2, int(accumulate), _stream())
+    _lib.call("dhaug_gemm_tn_bf16_rows", _p(A), la, _p(B), lb, _p(out), out.stride(0), _p(colsum), cr, M, N1, N2, int(accumulate), _stream())
     return out
 
 

@@ -325,7 +325,7 @@ def test_sweep4_in_two_parts_equals_one_part(M, tag):
 def test_bf16_operands_written_beside_fp32_results_equal_the_cast_launches(M):
     """dhaug_gp_assemble_bf16 / dhaug_gp_penalty_bf16 / the KCS operand of dhaug_kcs_forward: the bf16 tensors these launches write
     beside their fp32 results are, bit for bit, what dhaug_cast_pad_bf16 makes of those results (critic_step registers them as the
-    casts of those tensors: _Math.seed_cast)"""
+    casts of those tensors: _Bf16Math.seed_cast)"""
     from dhaug_amd import ops
     g = torch.Generator().manual_seed(3)
     for B, W in ((1000, 32), (2048 + 64, 48), (7, 48)):

@@ -408,7 +408,7 @@ def test_motion_critic_step_branch_layers_grouped_equals_layer_by_layer(M, tag, 
 def test_motion_critic_step_reads_no_unwritten_memory(M, tag, grouped, monkeypatch):
     """DenseDim 1000 is not a multiple of 16: the cotangent of a motion critic's concatenation is handed to the branches as 1000-wide
     column blocks that the backward GEMMs read 1008 wide (against zero columns of the weights' operand copy) -- the last row of the
-    last block used to be read 16 bytes beyond the allocation, and NaN x 0 = NaN (found in round 5; critic_step._Math.empty_blocks).
+    last block used to be read 16 bytes beyond the allocation, and NaN x 0 = NaN (found in round 5; critic_step._Bf16Math.empty_blocks).
     With every torch.empty buffer pre-filled with NaN / a huge value the step gives the same bits as without, in both launch forms."""
     from dhaug_amd.models_Fk_GAN import Fk_discriminator as dis
     from dhaug_amd import critic_step as CS
