@@ -87,8 +87,13 @@ SIGNATURES = {
     "dhaug_conv_taps_pack_bf16": [_vp, _i64, _i64, _i32, _vp, _i64, _vp, _i64, _vp],
     "dhaug_conv_taps_permute_f32": [_vp, _vp, _i64, _i64, _i32, _i32, _i32, _vp],
     "dhaug_tap_gather": [_vp, _i32, _i64, _i64, _i64, _i64, _i32, _i32, _i32, _vp, _i64, _vp, _i64, _vp],
+    "dhaug_graph_mix": [_vp, _i32, _i64, _vp, _vp, _vp, _i32, _i64, _i64, _i64, _i32, _vp],
+    "dhaug_graph_adj_grad": [_vp, _i32, _i64, _vp, _i32, _i64, _vp, _i32, _vp, _vp, _i64, _i64, _vp],
+    "dhaug_graph_wcat": [_vp, _vp, _i64, _i64, _i32, _vp],
 }
 BN_MAX_CHUNKS = 32                                     # DHAUG_BN_MAX_CHUNKS of include/dhaug.h
+GRAPH_MAX_PAIRS = 256                                  # DHAUG_GRAPH_MAX_PAIRS
+GRAPH_ADJ_WORKSPACE_DOUBLES = 64 * GRAPH_MAX_PAIRS     # DHAUG_GRAPH_ADJ_WORKSPACE_DOUBLES
 
 class MlpUnit(ctypes.Structure):
     """struct dhaug_mlp_unit (include/dhaug.h)"""

@@ -766,3 +766,66 @@ def conv_taps(x_rows, conv_weight, k, prec="bf16", out_f32=False):
     if not x_rows.is_contiguous():
         x_rows = x_rows.contiguous()
     return ConvTapsFn.apply(x_rows.view(M // k, k * C), conv_weight, prec, out_f32)
+
+
+# ---------------------------------------------------------------------------------------------------
+# SemGCN posenet: the joint mix of a semantic graph convolution, between A.linear (H = x Wcat^T) and A.bn_act
+# ---------------------------------------------------------------------------------------------------
+class GraphMixFn(torch.autograd.Function):
+    """z[b,i] = A[i,i] h0[b,i] + sum_{j != i} A[i,j] h1[b,j] + bias for H = [h0 | h1]: fp32 (M, 2C) -> fp32 (M, C), or bf16
+    (M, ceil16 2C) -> bf16 (M, ceil16 C).  A: the layer's (16, 16) adjacency, pairs: its nonzero pattern (int32 (nnz, 2) on the device).
+    Saved: H, A and the pairs.  First order only: dH by the adjoint launch, dA by dhaug_graph_adj_grad (zero off the pattern), dbias
+    by the column-sum kernel."""
+
+    @staticmethod
+    def forward(ctx, H, A, bias, pairs, C):
+        Ad = A.detach()
+        ctx.save_for_backward(H, Ad, pairs)
+        ctx.C = C
+        return ops.graph_mix(H, Ad, None if bias is None else bias.detach(), C)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gz):
+        H, A, pairs = ctx.saved_tensors
+        C = ctx.C
+        dH = dA = db = None
+        if ctx.needs_input_grad[0]:
+            dH = ops.graph_mix(gz, A, None, C, transpose=True, out_bf16=H.dtype == BF16)
+        if ctx.needs_input_grad[1]:
+            dA = ops.graph_adj_grad(gz, H, pairs, C)
+        if ctx.needs_input_grad[2]:
+            db = ops.colsum(gz if gz.stride(1) == 1 else gz.contiguous(), N=C)
+        return dH, dA, db, None, None
+
+
+def graph_mix(H, A, bias, pairs=None, C=None):
+    """the joint mix of H = [h0 | h1] through the (16, 16) adjacency A; pairs: A's pattern (default: every entry), C: the channels
+    (default: the bias's length, else half of H's columns)"""
+    if C is None:
+        C = bias.numel() if bias is not None else H.shape[1] // 2
+    if pairs is None:
+        idx = torch.arange(16, dtype=torch.int32, device=H.device)
+        pairs = torch.stack(torch.meshgrid(idx, idx, indexing="ij"), -1).reshape(256, 2).contiguous()
+    return GraphMixFn.apply(H, A, bias, pairs, C)
+
+
+class GraphWcatFn(torch.autograd.Function):
+    """Wcat (2 out, in) = [W[0]^T ; W[1]^T] of a SemGraphConv weight W (2, in, out): the B operand of H = x Wcat^T.  A copy; the
+    backward is the inverse permutation of the gradient."""
+
+    @staticmethod
+    def forward(ctx, W):
+        return ops.graph_wcat(W, True)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        return ops.graph_wcat(g.contiguous(), False)
+
+
+def graph_wcat(W):
+    """the (2 out, in) operand of a SemGraphConv weight; its packed copies are cached on the parameter (see _pack)"""
+    Wcat = GraphWcatFn.apply(W)
+    Wcat._dhaug_owner = W
+    return Wcat

@@ -58,3 +58,31 @@ def multi_frame_model_pos_preparation(args, dataset, device, flag='train'):
         model_pos.load_state_dict(torch.load(path, map_location=device)['model_pos'])
         print("posenet %s: weights loaded from %s" % (name, path))
     return model_pos
+
+
+GCN_POSENETS = ("gcn",)
+
+
+def gcn_model_pos_preparation(args, dataset, device, flag='train'):
+    """the reference's `gcn` branch (R/function_baseline/model_pos_preparation.py:28-30): the SemGCN posenet (B, 16, 2) -> (B, 16, 3),
+    SemGCN(adj, 128, num_layers=args.stages, p_dropout=args.dropout), the adjacency from dataset.skeleton() where the dataset has
+    one and from the 16-joint Human3.6M parents otherwise.  A factory of its own: model_pos_preparation above keeps refusing
+    every name but `videopose`."""
+    from ..models_baseline.gcn import H36M_PARENTS, SemGCN, adj_mx_from_parents, adj_mx_from_skeleton
+    name = args.posenet_name
+    if name not in GCN_POSENETS:
+        raise NotImplementedError("posenet_name %r is not a graph-convolution posenet of this package; implemented: %s"
+                                  % (name, ", ".join(GCN_POSENETS)))
+    skeleton = getattr(dataset, "skeleton", None)
+    adj = adj_mx_from_skeleton(skeleton()) if callable(skeleton) else adj_mx_from_parents(H36M_PARENTS)
+    model_pos = SemGCN(adj, 128, num_layers=int(args.stages), p_dropout=args.dropout, nodes_group=None).to(device)
+    count = sum(p.numel() for p in model_pos.parameters())
+    print("posenet %s: %d stages, %d parameters (%.2f M), precision %s" % (name, int(args.stages), count, count / 1e6, model_pos.precision))
+    if getattr(args, "pretrain", False):
+        path = getattr(args, "posenet_pretrain_path", None)
+        if not path:
+            raise ValueError("args.pretrain is set: give the checkpoint as args.posenet_pretrain_path")
+        model_pos.load_state_dict(torch.load(path, map_location=device)['model_pos'])
+        print("posenet %s: weights loaded from %s" % (name, path))
+    # else: the constructors' initialisation stays (the reference's init_weights touches nn.Linear modules only, and this model has none)
+    return model_pos

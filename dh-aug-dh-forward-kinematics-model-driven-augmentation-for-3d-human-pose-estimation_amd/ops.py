@@ -1309,3 +1309,95 @@ def tap_gather(x, nseq, t_in, C, k, dilation=1, stride=1, out_bf16=None, out_f32
     _lib.call("dhaug_tap_gather", _p(x), int(xb), x.stride(0), nseq, t_in, C, k, dilation, stride, _p(out_bf16),
               0 if out_bf16 is None else out_bf16.stride(0), _p(out_f32), 0 if out_f32 is None else out_f32.stride(0), _stream())
     return out_bf16, out_f32
+
+
+# ---------------------------------------------------------------------------------------------- SemGCN posenet: the joint mix
+def graph_adj_workspace(device=None):
+    """the per-workgroup partials of one adjacency gradient (DHAUG_GRAPH_ADJ_WORKSPACE_DOUBLES fp64; one call at a time)"""
+    return torch.empty(_lib.GRAPH_ADJ_WORKSPACE_DOUBLES, dtype=torch.float64, device=device if device is not None else "cuda")
+
+
+def _graph_rows(t, width, name, what):
+    """a (16 x poses, >= width) fp32 / bf16 matrix the graph kernels read where it lies, at any pitch and address (they take 16-byte
+    accesses only where both allow it): (tensor, row pitch)"""
+    if not t.is_cuda:
+        raise RuntimeError("dhaug op `%s` needs a GPU tensor (no CPU fallback exists)" % name)
+    if t.dim() != 2 or t.shape[1] < width or t.dtype not in (torch.float32, BF16):
+        raise ValueError("%s: %s must be a fp32 or bf16 (M, >= %d) matrix, got %s %s" % (name, what, width, t.dtype, tuple(t.shape)))
+    if t.shape[0] % 16:
+        raise ValueError("%s: %s must hold 16 rows per pose, got %d rows" % (name, what, t.shape[0]))
+    if t.stride(1) != 1 or t.stride(0) < width:
+        t = t.contiguous()
+    return t, t.stride(0)
+
+
+def _graph_vec(t, n, name, what, dtype=torch.float32):
+    if not (t.is_cuda and t.dtype == dtype and t.numel() == n and t.is_contiguous()):
+        raise ValueError("%s: %s must be a contiguous %s device tensor of %d elements" % (name, what, dtype, n))
+    return t
+
+
+def graph_mix(H, A, bias, C, transpose=False, out_bf16=None, out=None):
+    """dhaug_graph_mix.  Forward: H = [h0 | h1] (M, >= 2C), fp32 or bf16, a row-strided view allowed; A 16 x 16 fp32; bias (C,) fp32 or
+    None -> z[b,i] = A[i,i] h0[b,i] + sum_{j != i} A[i,j] h1[b,j] + bias, fp32 (M, C) or bf16 (M, ceil16 C) with a zero pad.
+    transpose: H is the cotangent g (M, >= C) -> dH (M, 2C) (bf16: ceil16(2C) columns), dh0[b,i] = A[i,i] g[b,i], dh1[b,j] =
+    sum_{i != j} A[i,j] g[b,i].  By default the output has the input's type; out: write into this matrix (a column block of a wider
+    buffer allowed; no column beyond its own is touched) instead of allocating."""
+    name = "graph_mix"
+    src, ld = _graph_rows(H, C if transpose else 2 * C, name, "g" if transpose else "H")
+    A = _graph_vec(A, 256, name, "A")
+    if bias is not None:
+        if transpose:
+            raise ValueError("graph_mix: the adjoint takes no bias")
+        bias = _graph_vec(bias, C, name, "bias")
+    width = 2 * C if transpose else C
+    M = src.shape[0]
+    if out is not None:
+        out_bf16 = out.dtype == BF16
+        need = ceil_to(width, 16) if out_bf16 else width
+        if not (out.is_cuda and out.dim() == 2 and out.dtype in (torch.float32, BF16) and out.shape == (M, need) and out.stride(1) == 1
+                and out.stride(0) >= need):
+            raise ValueError("graph_mix: out must be a fp32 or bf16 (%d, %d) matrix with contiguous rows, got %s %s"
+                             % (M, need, out.dtype, tuple(out.shape)))
+    else:
+        out_bf16 = (src.dtype == BF16) if out_bf16 is None else bool(out_bf16)
+        out = torch.empty((M, ceil_to(width, 16) if out_bf16 else width), dtype=BF16 if out_bf16 else torch.float32, device=src.device)
+    _lib.call("dhaug_graph_mix", _p(src), int(src.dtype == BF16), ld, _p(A), _p(bias), _p(out), int(out_bf16), out.stride(0), M, C,
+              int(bool(transpose)), _stream())
+    return out
+
+
+def graph_adj_grad(G, H, pairs, C, workspace=None, out=None):
+    """dhaug_graph_adj_grad: dA (16, 16) fp32 with dA[i,j] = sum_{b,c} G[b,i,c] (i == j ? h0 : h1)[b,j,c] at the pairs (i, j) listed in
+    `pairs` (int32 (nnz, 2) on the device, nnz <= 256) and exactly 0 elsewhere; fp64 sums in a fixed order"""
+    name = "graph_adj_grad"
+    g, ld_g = _graph_rows(G, C, name, "G")
+    h, ld_h = _graph_rows(H, 2 * C, name, "H")
+    if g.shape[0] != h.shape[0]:
+        raise ValueError("graph_adj_grad: G and H differ in rows, %d and %d" % (g.shape[0], h.shape[0]))
+    if pairs.dim() != 2 or pairs.shape[1] != 2 or pairs.shape[0] > _lib.GRAPH_MAX_PAIRS:
+        raise ValueError("graph_adj_grad: pairs must be (nnz <= %d, 2), got %s" % (_lib.GRAPH_MAX_PAIRS, tuple(pairs.shape)))
+    pairs = _graph_vec(pairs, pairs.numel(), name, "pairs", torch.int32)
+    ws = workspace if workspace is not None else graph_adj_workspace(g.device)
+    assert ws.is_cuda and ws.dtype == torch.float64 and ws.numel() >= _lib.GRAPH_ADJ_WORKSPACE_DOUBLES
+    dA = torch.empty((16, 16), dtype=torch.float32, device=g.device) if out is None else _graph_vec(out, 256, name, "out")
+    _lib.call("dhaug_graph_adj_grad", _p(g), int(g.dtype == BF16), ld_g, _p(h), int(h.dtype == BF16), ld_h, _p(pairs), pairs.shape[0],
+              _p(dA), _p(ws), g.shape[0], C, _stream())
+    return dA
+
+
+def graph_wcat(src, to_cat=True):
+    """dhaug_graph_wcat: W (2, in, out) -> Wcat (2 out, in) = [W[0]^T ; W[1]^T]; to_cat False: the adjoint, (2 out, in) -> (2, in, out)"""
+    s = _graph_vec(src.detach(), src.numel(), "graph_wcat", "src")
+    if to_cat:
+        if s.dim() != 3 or s.shape[0] != 2:
+            raise ValueError("graph_wcat: W must be (2, in, out), got %s" % (tuple(s.shape),))
+        n_in, n_out = s.shape[1], s.shape[2]
+        dst = torch.empty((2 * n_out, n_in), dtype=torch.float32, device=s.device)
+    else:
+        if s.dim() != 2 or s.shape[0] % 2:
+            raise ValueError("graph_wcat: Wcat must be (2 out, in), got %s" % (tuple(s.shape),))
+        n_out, n_in = s.shape[0] // 2, s.shape[1]
+        dst = torch.empty((2, n_in, n_out), dtype=torch.float32, device=s.device)
+    _lib.call("dhaug_graph_wcat", _p(s), _p(dst), n_in, n_out, int(bool(to_cat)), _stream())
+    return dst

@@ -940,6 +940,44 @@ int dhaug_conv_taps_permute_f32(const float* src, float* dst, int64_t N, int64_t
 int dhaug_tap_gather(const void* x, int x_bf16, int64_t ld_x, int64_t nseq, int64_t t_in, int64_t C, int k, int dilation,
                      int stride, uint16_t* out_bf16, int64_t ld_ob, float* out_f32, int64_t ld_of, void* stream);
 
+/* ------------------------------------------------------------------------------------------------------
+ * SemGCN posenet: the joint mix of a semantic graph convolution (R/models_baseline/gcn/sem_graph_conv.py; csrc/dhaug_graph.hip)
+ * ----------------------------------------------------------------------------------------------------
+ * Activations are rows, pose-major then joint: row 16 b + i is joint i of pose b, M = 16 x poses (DHAUG_EINVAL otherwise).  A is the
+ * layer's 16 x 16 adjacency, fp32, row-major, on the device.  With H = x Wcat^T = [h0 | h1] (M, 2C) from the GEMM in front,
+ *     z[b,i,:] = A[i,i] h0[b,i,:] + sum_{j != i} A[i,j] h1[b,j,:] + bias           (the diagonal term first, then j ascending, fmaf, fp32).
+ * dhaug_graph_mix, transpose = 0: src = H (M, ld_src >= 2C), fp32 (src_bf16 = 0) or bf16 (1); bias C fp32 or NULL; dst = z, fp32
+ *   (M, ld_dst >= C) or bf16 (M, ld_dst >= ceil16 C) with columns [C, ceil16 C) written as zeros (the next GEMM's operand).
+ *   transpose = 1, the adjoint: src = g (M, ld_src >= C), dst = dH (M, ld_dst >= 2C; bf16: >= ceil16(2C), the pad written as zeros),
+ *     dh0[b,i,:] = A[i,i] g[b,i,:],   dh1[b,j,:] = sum_{i != j} A[i,j] g[b,i,:]     (i ascending); bias must be NULL.
+ *   The own row's term enters the off-diagonal sum with weight 0, as in the reference's dense products (it matters only to a row that
+ *   holds inf or NaN).  One rounding on a bf16 output.  No column of a source row at or beyond 2C (C) is read, none of dst beyond the pad written.
+ *   ALIGNMENT: none beyond the element's own.  The kernel takes 16-byte accesses only where it finds both bases, both pitches and
+ *   C x element size on the 16-byte grid, and goes element by element otherwise (any C >= 1, e.g. the output layer's C = 3, ld 6).
+ *   A and bias are read element by element always: they may lie on any 4-byte boundary (tensors of odd size in PosenetAdam's flat
+ *   buffer).  No atomics: the same call gives the same bits.
+ * dhaug_graph_adj_grad: the gradient of A.  g (M, ld_g >= C), h = H (M, ld_h >= 2C), each fp32 or bf16; pairs: device, nnz x (i, j)
+ *   int32, 0 <= nnz <= DHAUG_GRAPH_MAX_PAIRS; dA: 16 x 16 fp32.  At every listed pair
+ *     dA[i,j] = sum_{b,c} g[b,i,c] (i == j ? h0 : h1)[b,j,c],
+ *   and EXACTLY 0 at every other entry (all 256 are written; a pair outside [0, 16) names no entry and is ignored).  Every product
+ *   is formed and summed in fp64: per workgroup in a fixed order into workspace (device, DHAUG_GRAPH_ADJ_WORKSPACE_DOUBLES doubles,
+ *   8-byte aligned; one call at a time per workspace), then a second launch adds the partials in workgroup order and rounds once.  No
+ *   atomics: two calls give the same bits.  Element accesses only.
+ * dhaug_graph_wcat: to_cat = 1: src = W (2, in, out) -> dst = Wcat (2 out, in), Wcat[k out + n, c] = W[k, c, n] (the B operand of
+ *   H = x Wcat^T); to_cat = 0 the adjoint, src = dWcat -> dst = dW.  fp32, both contiguous, a copy (exact).  src != dst.
+ * All three: DHAUG_EINVAL for a negative size, a flag outside {0, 1}, a NULL required pointer, M % 16 != 0, nnz outside its range;
+ * DHAUG_EALIGN for a leading dimension below its minimum or a pointer off its element's grid; DHAUG_EUNSUPPORTED for C, in, out >= 2^28,
+ * in x out >= 2^30; an empty problem (M = 0 or C = 0; in = 0 or out = 0) is a no-op that looks at no pointer. */
+#define DHAUG_GRAPH_MIX_MAX_BLOCKS 512       /* workgroups of 256 items a mix launch takes at most: more items, more passes per thread */
+#define DHAUG_GRAPH_MAX_PAIRS 256
+#define DHAUG_GRAPH_ADJ_MAX_BLOCKS 64
+#define DHAUG_GRAPH_ADJ_WORKSPACE_DOUBLES (DHAUG_GRAPH_ADJ_MAX_BLOCKS * DHAUG_GRAPH_MAX_PAIRS)
+int dhaug_graph_mix(const void* src, int src_bf16, int64_t ld_src, const float* A, const float* bias, void* dst, int dst_bf16,
+                    int64_t ld_dst, int64_t M, int64_t C, int transpose, void* stream);
+int dhaug_graph_adj_grad(const void* g, int g_bf16, int64_t ld_g, const void* h, int h_bf16, int64_t ld_h, const int32_t* pairs,
+                         int nnz, float* dA, void* workspace, int64_t M, int64_t C, void* stream);
+int dhaug_graph_wcat(const float* src, float* dst, int64_t in, int64_t out, int to_cat, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,96 @@
+"""The SemGCN posenet's training step and evaluation forward at batch 1 024, hid 128, 4 blocks, dropout 0.25.
+
+Variants: "stock" = the plain-torch restatement of tests/gcn_util.py (StockGCN, fp32), and models_baseline.gcn.SemGCN in each
+precision ("bf16", "bf16x3", "bf16x6").  Every variant takes its steps through function_aug.model_pos_train.StepRunner with the fused
+loss and PosenetAdam, so the difference between two lines is the network's forward and backward alone.
+
+All variants in ONE process, warmed up, then alternating: five rounds, every variant --steps training steps (and --steps evaluation
+forwards under no_grad) per round between HIP events on the stream; the median of a variant's five rounds is reported, with the
+rounds behind it.  No speed is promised: the network has 0.27 M parameters and its step is a chain of small launches.
+
+    python tools/time_gcn.py [--steps 50]"""
+import argparse
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+import numpy as np
+import torch
+import torch.nn as nn
+
+import dhaug_amd  # noqa: F401
+from dhaug_amd.function_aug import model_pos_train as T
+from dhaug_amd.models_baseline.gcn import H36M_PARENTS, SemGCN, adj_mx_from_parents
+import gcn_util as CU
+
+B, HID, BLOCKS, DROPOUT = 1024, 128, 4, 0.25
+VARIANTS = ("stock", "bf16", "bf16x3", "bf16x6")
+
+
+def build(variant):
+    torch.manual_seed(0)
+    if variant == "stock":
+        return CU.StockGCN(HID, BLOCKS, DROPOUT).cuda()
+    model = SemGCN(adj_mx_from_parents(H36M_PARENTS), HID, num_layers=BLOCKS, p_dropout=DROPOUT).cuda()
+    model.precision = variant
+    return model
+
+
+def runners(variant, steps):
+    """(train, evaluate): `steps` optimizer steps / `steps` evaluation forwards on fixed device batches"""
+    g = torch.Generator(device="cuda").manual_seed(1)
+    x = torch.randn(B, 16, 2, device="cuda", generator=g) * 0.4
+    t = torch.randn(B, 16, 3, device="cuda", generator=g) * 0.3
+    model = build(variant)
+    run = T.StepRunner(model, T.posenet_optimizer(model, 1e-4), nn.MSELoss(reduction="mean"), torch.device("cuda"))
+
+    def train():
+        model.train()
+        with torch.enable_grad():
+            for _ in range(steps):
+                run.step(x, t, "loss", B)
+
+    def evaluate():
+        model.eval()
+        with torch.no_grad():
+            for _ in range(steps):
+                model(x)
+
+    return train, evaluate
+
+
+def timed(fn):
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    torch.cuda.synchronize()
+    e0.record()
+    fn()
+    e1.record()
+    e1.synchronize()
+    return e0.elapsed_time(e1)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--steps", type=int, default=50)
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("tools/time_gcn.py needs a GPU: a time taken anywhere else says nothing")
+    runs = {v: runners(v, a.steps) for v in VARIANTS}
+    for train, evaluate in runs.values():                           # warm-up: every shape the timed windows use
+        train(), evaluate()
+    ts = {(v, k): [] for v in VARIANTS for k in ("train", "eval")}
+    for _ in range(5):
+        for v, (train, evaluate) in runs.items():
+            ts[(v, "train")].append(timed(train) / a.steps)
+            ts[(v, "eval")].append(timed(evaluate) / a.steps)
+    for k, what in (("train", "training step (forward, loss, backward, clip + Adam)"), ("eval", "evaluation forward")):
+        for v in VARIANTS:
+            r = ts[(v, k)]
+            print("gcn=%-6s: %.3f ms per %s at B = %d (median of 5 alternating rounds of %d; rounds %s)"
+                  % (v, float(np.median(r)), what, B, a.steps, " ".join("%.3f" % q for q in r)), flush=True)
+
+
+if __name__ == "__main__":
+    main()
