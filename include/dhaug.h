@@ -584,6 +584,21 @@ int dhaug_pack_wfrag(const float* W, int64_t ldw, uint16_t* dst, int64_t N, int6
 #define DHAUG_MLP_LOAD_BF16   1   /* global bf16 (M, ld) columns [0, cols) -> buffer dst                              */
 #define DHAUG_MLP_STORE_BF16  2   /* buffer src columns [0, cols) -> global bf16 (M, ld)                              */
 #define DHAUG_MLP_GEMM        3   /* one layer: dst = act(W * src [+ W2 * src2] + bias + res)                          */
+/* Where a GEMM unit rounds.  Products of bf16 operands, the fp32 bias and the residual (a bf16 value, added as 1.0 * res on the
+ * matrix unit) are accumulated in fp32.  The activation is applied to that fp32 value (LeakyReLU: max(v, v * slope) in fp32; ReLU
+ * may be taken after the rounding, which gives the same bf16 value), and the result is rounded ONCE, to nearest even, to bf16 when
+ * it goes to an LDS buffer -- whence a later GEMM, a STORE_BF16 or a `save` target takes it unchanged -- or into the dot product
+ * of a DOT_OUT unit: that epilogue rounds and activates the features exactly as it would have stored them, multiplies them by w2
+ * in fp32 (fmaf) and adds the folded bias.  An OUT_F32 result is not rounded: act(.) leaves as the fp32 value the accumulator
+ * held; such a unit takes no residual (res >= 0: DHAUG_EINVAL).  A LOAD_F32 rounds its input to bf16 the same way.  With data for
+ * which every partial sum is an fp32 value (tests/mlp_unit_util.py) a program's output is therefore one definite bit pattern,
+ * whatever route its units take.
+ * A unit writes whole 32-feature slices: columns [0, 32 * ceil(n / 32)) of dst, the ones beyond n as act(res) (zero weights and
+ * bias).  What the columns beyond hold afterwards is unspecified (a run of full-width layers writes all 256, a layer on its own
+ * leaves them as they were); a consumer reads whole 64-column chunks under zero weights there, so they must hold finite values.
+ * For the run planner a layer with n > 224 (eight slices) counts as full width: its consumer is handed ksteps = 16, with zero
+ * weight columns beyond n.  A second source starts on a chunk boundary of the first (ksteps % 4 == 0) and the two take 1 + 1,
+ * 2 + 2 or 4 + 4 chunks: fewer columns in the second source are loaded and packed as whole chunks of the first's count. */
 #define DHAUG_MLP_LOAD_KCS    5   /* dhaug_mlp_forward_x3 only: global fp32 poses (M, ld >= 48) -> their 30 KCS features  */
                                   /* (special_KCS_Input_transform, R/models_Fk_GAN/Fk_discriminator.py:36-146) in buffer   */
                                   /* dst, columns 30..63 zero: the 3D critic's KCS branch without a launch of its own        */
