@@ -89,6 +89,12 @@ def pack_key(W):
     return (W.data_ptr(), W._version, tuple(W.shape), WEIGHT_EPOCH, getattr(W, "_dhaug_epoch", 0), CAPTURE_ID)
 
 
+def tensor_state(t):
+    """what a cache built from a tensor's VALUES compares: where it lies, torch's version counter, and the epoch the optimizers
+    advance when they write through raw pointers"""
+    return (t.data_ptr(), t._version, getattr(t, "_dhaug_epoch", 0))
+
+
 def install_packed(W, nt, nn):
     """the optimizer re-packed W itself (dhaug_repack_weights): register the fresh bf16 copies under the current key"""
     ent = _Packed()

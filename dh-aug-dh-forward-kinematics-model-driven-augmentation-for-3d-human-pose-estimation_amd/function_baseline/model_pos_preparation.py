@@ -1,11 +1,29 @@
 """Drop-in for R/function_baseline/model_pos_preparation.py (model_pos_preparation :18-87): builds the posenet the augmentation
-trains.  Of the reference's five posenet names this package implements `videopose`, the default run's single-frame model."""
+trains.  Of the reference's five posenet names this package implements three, each through a factory of its own: `videopose` (the
+default run's single-frame model, model_pos_preparation), `mulit_farme_videopose` (multi_frame_model_pos_preparation) and `gcn`
+(gcn_model_pos_preparation).  `mlp` and `mulit_farme_poseformer` are not implemented."""
 import torch
 
 from ..models_baseline.videopose.model_VideoPose3D import TemporalModelOptimized1f
 
 POSENETS = ("videopose",)
 REFERENCE_POSENETS = ("gcn", "mlp", "videopose", "mulit_farme_videopose", "mulit_farme_poseformer")
+
+
+def _finish(args, name, model_pos, device, described):
+    """the factories' common tail: the line that describes the model (`described` with the parameter count and the precision put
+    behind it), then, with args.pretrain, ckpt['model_pos'] of args.posenet_pretrain_path; otherwise the constructors'
+    initialisation stays (the reference applies its init_weights here, which touches nn.Linear modules only, and these models hold
+    none)"""
+    count = sum(p.numel() for p in model_pos.parameters())
+    print("posenet %s, %d parameters (%.2f M), precision %s" % (described, count, count / 1e6, model_pos.precision))
+    if getattr(args, "pretrain", False):
+        path = getattr(args, "posenet_pretrain_path", None)
+        if not path:
+            raise ValueError("args.pretrain is set: give the checkpoint as args.posenet_pretrain_path")
+        model_pos.load_state_dict(torch.load(path, map_location=device)['model_pos'])
+        print("posenet %s: weights loaded from %s" % (name, path))
+    return model_pos
 
 
 def model_pos_preparation(args, dataset, device, flag='train'):
@@ -17,17 +35,7 @@ def model_pos_preparation(args, dataset, device, flag='train'):
         raise NotImplementedError("posenet_name %r (%s) is not implemented; implemented: %s" % (name, known, ", ".join(POSENETS)))
     widths = [1] * (int(args.stages) + 1)
     model_pos = TemporalModelOptimized1f(16, 2, 15, filter_widths=widths, causal=False, dropout=0.25, channels=1024).to(device)
-    count = sum(p.numel() for p in model_pos.parameters())
-    print("posenet %s: %d stages, %d parameters (%.2f M), precision %s" % (name, len(widths) - 1, count, count / 1e6, model_pos.precision))
-    if getattr(args, "pretrain", False):
-        path = getattr(args, "posenet_pretrain_path", None)
-        if not path:
-            raise ValueError("args.pretrain is set: give the checkpoint as args.posenet_pretrain_path")
-        model_pos.load_state_dict(torch.load(path, map_location=device)['model_pos'])
-        print("posenet %s: weights loaded from %s" % (name, path))
-    # else: torch's default initialisation stays.  (The reference applies its init_weights here, which touches nn.Linear modules
-    # only; this model holds nn.Conv1d and nn.BatchNorm1d modules and no nn.Linear, so it is a no-op there as well.)
-    return model_pos
+    return _finish(args, name, model_pos, device, "%s: %d stages" % (name, len(widths) - 1))
 
 
 MULTI_FRAME_POSENETS = ("mulit_farme_videopose",)
@@ -48,16 +56,8 @@ def multi_frame_model_pos_preparation(args, dataset, device, flag='train'):
     widths = [int(w) for w in str(args.architecture).split(',')]
     cls = multiFrame_TemporalModelOptimized1f if flag == "train" else multiFrame_TemporalModel
     model_pos = cls(16, 2, 16, filter_widths=widths, causal=False, dropout=0.25, channels=1024).to(device)
-    count = sum(p.numel() for p in model_pos.parameters())
-    print("posenet %s (%s): filter widths %s, receptive field %d, %d parameters (%.2f M), precision %s"
-          % (name, cls.__name__, widths, model_pos.receptive_field(), count, count / 1e6, model_pos.precision))
-    if getattr(args, "pretrain", False):
-        path = getattr(args, "posenet_pretrain_path", None)
-        if not path:
-            raise ValueError("args.pretrain is set: give the checkpoint as args.posenet_pretrain_path")
-        model_pos.load_state_dict(torch.load(path, map_location=device)['model_pos'])
-        print("posenet %s: weights loaded from %s" % (name, path))
-    return model_pos
+    return _finish(args, name, model_pos, device,
+                   "%s (%s): filter widths %s, receptive field %d" % (name, cls.__name__, widths, model_pos.receptive_field()))
 
 
 GCN_POSENETS = ("gcn",)
@@ -76,13 +76,4 @@ def gcn_model_pos_preparation(args, dataset, device, flag='train'):
     skeleton = getattr(dataset, "skeleton", None)
     adj = adj_mx_from_skeleton(skeleton()) if callable(skeleton) else adj_mx_from_parents(H36M_PARENTS)
     model_pos = SemGCN(adj, 128, num_layers=int(args.stages), p_dropout=args.dropout, nodes_group=None).to(device)
-    count = sum(p.numel() for p in model_pos.parameters())
-    print("posenet %s: %d stages, %d parameters (%.2f M), precision %s" % (name, int(args.stages), count, count / 1e6, model_pos.precision))
-    if getattr(args, "pretrain", False):
-        path = getattr(args, "posenet_pretrain_path", None)
-        if not path:
-            raise ValueError("args.pretrain is set: give the checkpoint as args.posenet_pretrain_path")
-        model_pos.load_state_dict(torch.load(path, map_location=device)['model_pos'])
-        print("posenet %s: weights loaded from %s" % (name, path))
-    # else: the constructors' initialisation stays (the reference's init_weights touches nn.Linear modules only, and this model has none)
-    return model_pos
+    return _finish(args, name, model_pos, device, "%s: %d stages" % (name, int(args.stages)))

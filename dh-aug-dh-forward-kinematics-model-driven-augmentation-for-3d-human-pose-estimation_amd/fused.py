@@ -195,7 +195,7 @@ class FusedNet:
         from . import autograd_ops as A
         if self.params is None:                                # (walking the module tree costs more than the launch)
             self.params = list(self.module.parameters())
-        key = (A.WEIGHT_EPOCH, A.CAPTURE_ID) + tuple((p.data_ptr(), p._version, getattr(p, "_dhaug_epoch", 0)) for p in self.params)
+        key = (A.WEIGHT_EPOCH, A.CAPTURE_ID) + tuple(A.tensor_state(p) for p in self.params)
         if key != self.key:
             ptrs = tuple(p.data_ptr() for p in self.params)
             if self.layers is not None and self.mode == "bf16" and ptrs == self.ptrs:

@@ -29,10 +29,6 @@ PRECISIONS = ("bf16", "bf16x3", "bf16x6")
 JOINTS = 16              # the joints dhaug_graph_mix mixes
 
 
-def _state(t):
-    return (t.data_ptr(), t._version, getattr(t, "_dhaug_epoch", 0))
-
-
 class _GraphConv(nn.Module):
     """parameter holder: .gconv, .bn (and the dropout probability, read as .dropout.p)"""
 
@@ -157,9 +153,9 @@ class SemGCN(nn.Module):
     def _eval_key(self):
         key = [self._arithmetic(), self._stat_epoch]
         for conv in self._convs():
-            key += [A.pack_key(conv.W), _state(conv.e), None if conv.bias is None else _state(conv.bias)]
+            key += [A.pack_key(conv.W), A.tensor_state(conv.e), None if conv.bias is None else A.tensor_state(conv.bias)]
         for _, bn, _, _ in self._layers():
-            key += [_state(bn.weight), _state(bn.bias), _state(bn.running_mean), _state(bn.running_var), bn.eps]
+            key += [A.tensor_state(t) for t in (bn.weight, bn.bias, bn.running_mean, bn.running_var)] + [bn.eps]
         return key
 
     def _eval_state(self):

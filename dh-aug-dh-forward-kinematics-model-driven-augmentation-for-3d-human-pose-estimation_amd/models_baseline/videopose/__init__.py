@@ -1,1 +1,1 @@
-"""videopose: the single-frame VideoPose posenet on this package's kernels."""
+"""videopose: the VideoPose posenets (single-frame, and the base of the multi-frame classes) on this package's kernels."""

@@ -267,6 +267,61 @@ def test_evaluation_cache(D):
         assert torch.equal(y4, evaluate(make(D, cfg, prec, state=model.state_dict()), x))
 
 
+def test_single_frame_is_the_strided_model_at_k1(D):
+    """the single-frame class and the strided multi-frame class with every filter width 1, one state: bit-equal evaluation outputs,
+    training outputs, gradients and BatchNorm buffers in 'bf16' and 'bf16x3'.  'bf16x6' is the one intended difference (the
+    multi-frame class runs it as autograd_ops.ORDERED6, two launches per product), pinned by the count of GEMM launches"""
+    from dhaug_amd.models_Fk_GAN.mulit_farme_videopose import multiFrame_TemporalModelOptimized1f
+    cfg = NU.SMALL
+    widths = [1] * (cfg["stages"] + 1)
+    x, t = NU.make_inputs(96, 5)
+    x, t = x.cuda(), t.cuda()
+
+    def pair(prec):
+        models = (D.Model(16, 2, 15, widths, channels=cfg["C"]), multiFrame_TemporalModelOptimized1f(16, 2, 15, widths, channels=cfg["C"]))
+        for m in models:
+            m.load_state_dict(NU.seeded_state(cfg["C"], cfg["stages"], cfg["seed"]), strict=True)
+            m.precision = prec
+            m.cuda()
+        return models
+
+    for prec in ("bf16", "bf16x3"):
+        single, multi = pair(prec)
+        assert torch.equal(evaluate(single, x)[:, 1:], evaluate(multi, x[:, None])[:, 0]), prec
+        single.train(), multi.train()
+        torch.manual_seed(7)
+        a = single(x)[:, 1:]
+        torch.manual_seed(7)
+        b = multi(x[:, None])[:, 0]
+        assert torch.equal(a, b), prec
+        nn.functional.mse_loss(a, t[:, 1:]).backward()
+        nn.functional.mse_loss(b, t[:, 1:]).backward()
+        for (k, p), q in zip(single.named_parameters(), multi.parameters()):
+            assert p.grad is not None and torch.equal(p.grad, q.grad), (prec, k)
+        buffers = list(zip(single.named_buffers(), multi.buffers()))
+        assert len(buffers) == 3 * (2 * cfg["stages"] + 1)
+        for (k, p), q in buffers:
+            assert torch.equal(p, q), (prec, k)
+        assert int(single.expand_bn.num_batches_tracked) == 1
+
+    gemms = []
+    orig = D.lib.call
+
+    def counting(name, *a):
+        gemms[-1] += name == "dhaug_gemm_bf16"
+        return orig(name, *a)
+
+    for m, inp in zip(pair("bf16x6"), (x, x[:, None])):
+        gemms.append(0)
+        D.lib.call = counting
+        try:
+            evaluate(m, inp)
+        finally:
+            D.lib.call = orig
+    figure("k1_gemm_launches_single", gemms[0]), figure("k1_gemm_launches_multi", gemms[1])
+    assert gemms[0] == 2 * cfg["stages"] + 2 and gemms[1] > gemms[0]
+
+
 def low_precision_figures(rec, G, which, M):
     fig = dict(grad=0.0)
     for i, (n, v) in enumerate(rec):

@@ -62,6 +62,21 @@ def test_state_dict_layout_is_the_references(built, G):
     assert m.precision in ("bf16", "bf16x3", "bf16x6", "f16x3")
 
 
+def test_single_frame_is_the_strided_model_at_k1(built):
+    """the single-frame class and the strided multi-frame class with every filter width 1, built under one seed: the same keys in
+    the same order, the same shapes and the same initial values (one constructor, one order of creation and of random draws)"""
+    from dhaug_amd.models_baseline.videopose.model_VideoPose3D import TemporalModelOptimized1f
+    from dhaug_amd.models_Fk_GAN.mulit_farme_videopose import multiFrame_TemporalModelOptimized1f
+    states = []
+    for cls in (TemporalModelOptimized1f, multiFrame_TemporalModelOptimized1f):
+        torch.manual_seed(3)
+        states.append(cls(16, 2, 15, [1] * 3, channels=64).state_dict())
+    assert list(states[0].keys()) == list(states[1].keys()) == list(NU.shapes(64, 2).keys())
+    for k, a in states[0].items():
+        b = states[1][k]
+        assert a.shape == b.shape and a.dtype == b.dtype and torch.equal(a, b), k
+
+
 def test_state_round_trips_through_stock_modules(built):
     cfg = NU.SMALL
     m = make(built, cfg)
