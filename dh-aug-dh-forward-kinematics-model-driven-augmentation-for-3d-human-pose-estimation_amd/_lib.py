@@ -159,6 +159,8 @@ SIGNATURES["dhaug_pack_wfrag"] = [_vp, _i64, _vp, _i64, _i64, _i64, _vp]
 SIGNATURES["dhaug_pack_wfrag_batch"] = [_vp, _i32, _vp]
 SIGNATURES["dhaug_pack_wfrag_composed"] = [_vp, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _vp]
 SIGNATURES["dhaug_mlp_forward"] = [ctypes.POINTER(MlpUnit), _i32, _i64, _vp]
+SIGNATURES["dhaug_mlp_plan"] = [ctypes.POINTER(MlpUnit), _i32, _i64, ctypes.POINTER(ctypes.c_int32)]
+MLP_PLAN_STACK, MLP_PLAN_LEADG = 1 << 13, 1 << 15      # DHAUG_MLP_PLAN_* of include/dhaug.h
 SIGNATURES["dhaug_pack_wfrag_f16x2"] = [_vp, _i64, _vp, _i64, _i64, _i64, _vp]
 SIGNATURES["dhaug_pack_wfrag_f16x2_t16"] = [_vp, _i64, _vp, _i64, _i64, _i64, _vp]
 SIGNATURES["dhaug_mlp_forward_x3"] = [ctypes.POINTER(MlpUnit), _i32, _i64, _vp]

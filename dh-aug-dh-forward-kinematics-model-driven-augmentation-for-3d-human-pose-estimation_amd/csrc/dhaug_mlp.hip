@@ -79,6 +79,10 @@ struct Unit {
 // source 1), 24-27 feature slices
 enum { PLAN_STACK = 1 << 13, PLAN_LEAKY = 1 << 10, PLAN_ALT = 1 << 11, PLAN_TAIL = 1 << 12, PLAN_TAIL_BF16 = 1 << 14, PLAN_OUT = 1 << 28,
        PLAN_DOT = 1 << 29, PLAN_PAIR = 1 << 30 };                            // PAIR: this unit and the next run as one (gemm_pair)
+// plan of a bf16 LOAD.  Bit 0: the program parks rows with a STORE (full barrier first).  PLAN_LEADG: the LOAD and the stack whose
+// lead layer it feeds run as ONE dispatch and the lead takes its operand from global memory (stack_lead_global); the rest of the
+// word is then that stack's plan with the lead's true k-steps (cols / 16: 2 or 3) in bits 0-3
+enum { PLAN_LEADG = 1 << 15 };
 
 struct Program {
     int nunits;
@@ -595,6 +599,9 @@ __device__ __forceinline__ void stack_layer(const StackDesc& d, const StackDesc&
     }
     typedef unsigned char __attribute__((address_space(3))) * LdsWPtr;
     // elements j, j+1 (j even) of a tile held in `a`: j = 16t + 4g + e -> activation, packed bf16 pair
+    // (KEEP IN STEP with stack_lead_global: it has its own copy of lep / wa / pair_pack / quad_store and of the dealing of the next
+    // layer's fragments and seed -- a change to the epilogue, the swizzle or that hand-over is made in both; the GPU tests of
+    // tests/test_gpu_mlp_lead_global.py compare the two routes bit for bit)
     auto pair_pack = [&](const f32x16 (&a)[MLP_NS], int j) -> uint32_t {
         const int t = j >> 4, g = (j >> 2) & 3, e = j & 3;
         const float v0 = a[t][4 * g + e], v1 = a[t][4 * g + e + 1];
@@ -764,6 +771,137 @@ __device__ __forceinline__ void stack_layer(const StackDesc& d, const StackDesc&
     for (int t = 0; t < MLP_NS; ++t) seed[t] = nseed[t];
 }
 
+// The operand of a stack's lead layer straight from global memory (planner: PLAN_LEADG).  A bf16 LOAD of 32 or 48 columns that
+// feeds nothing but the lead was a latency chain of its own in front of every stack -- global -> VGPR, ds_write, barrier, the
+// next unit's dispatch, and only then the lead's bias and weight requests: two L2 round trips one after the other for 8 or 12 KB
+// per tile (unit stamps: 1 588 / 2 780 / 1 752 clocks for the critics' three LOADs).  But the B fragment of
+// v_mfma_f32_32x32x16_bf16 of lane (r31, h) at k-step k is eight consecutive bf16 of ONE row: byte (32 mt + r31) * ld * 2 + 32 k +
+// 16 h of the tile, an aligned 16-byte load.  So the lane fetches its fragments itself, all row tiles and k-steps up front and IN
+// FRONT of the lead's bias and weight requests (vmcnt retires in order: operand first, then weights -- one round trip), and the
+// LDS image, its barrier and the LOAD's dispatch are gone.  The four waves read the same 2-3 KB per 32 rows; L1 serves three of them.
+//   * one buffer resource over rows [m0, min(m0 + 128, M)) whose records end behind the last row's `cols` columns: rows beyond M
+//     come back as zeros from the range check (which sees the per-lane offset, so the row tile is part of THAT, not a scalar
+//     offset) -- no branch, and no byte outside the tensor is read;
+//   * exactly cols / 16 k-steps: the LOAD's zero fill to 64 columns met zero weights (the blob stays packed in whole chunks; the
+//     lead uses its first k-steps).  Never a load of the 16 bytes behind the row: they belong to the next row, and a NaN there
+//     times a zero weight is a NaN.
+template <int KS>
+__device__ __forceinline__ void lead_operand(UnitPtr lu, long long m0, long long M, int lane, bf16x8 (&gx)[MLP_MT][KS]) {
+    const long long ld = lu->ld, left = M - m0;                              // (ld <= 2^20: checked by the planner)
+    const int rows = left < MLP_BM ? (int)left : MLP_BM, ldb = (int)ld * 2;
+    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
+        const_cast<uint16_t*>(static_cast<const uint16_t*>(lu->g)) + m0 * ld, 0, (rows - 1) * ldb + 32 * KS, 0x27000);
+    const int off = (lane & 31) * ldb + ((lane >> 5) << 4);
+#pragma unroll
+    for (int mt = 0; mt < MLP_MT; ++mt)
+#pragma unroll
+        for (int k = 0; k < KS; ++k)
+            gx[mt][k] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(rs, off + 32 * mt * ldb + 32 * k, 0, 0));
+}
+
+// The lead form of stack_layer for such an operand: the same arithmetic (bias seeds the accumulators, k ascending, the epilogue
+// of tile mt - 1 behind the MFMAs of tile mt, the next layer's fragments during tiles 1 and 2: `nlo` low half, `whi` high half),
+// with the activation fragments in `gx` instead of LDS reads.  A tile is 2 KS matrix instructions; the eight ds_write_b64 of the
+// previous tile and the sixteen fragment requests are dealt out evenly over them.  `wl`: the lead's own fragments, k-steps < KS.
+// KEEP IN STEP with stack_layer: lep / wa (the swizzled epilogue addresses), pair_pack, quad_store, the ABL_ hooks and the hand-over
+// of the next layer's fragments and seed are copies of its LEAD form, not shared code (stack_layer also compiles into the
+// forward-with-save unit, whose device code this route must not move); tests/test_gpu_mlp_lead_global.py holds the two routes
+// to the same bits.
+template <bool LEAKY, int KS>
+__device__ __forceinline__ void stack_lead_global(const StackDesc& d, const StackDesc& nd, unsigned char* smem, int wave, int lane,
+                                                  const bf16x8 (&gx)[MLP_MT][KS], const WHalf& wl, WHalf& nlo, WHalf& whi,
+                                                  f32x16 (&seed)[MLP_NS], int dbg) {
+    DHAUG_LSTAMP(dbg)
+    static_assert(KS == 2 || KS == 3, "32 or 48 columns");
+    constexpr int TILE_BYTES = 32 * BUF01_PITCH * 2, NM = MLP_NS * KS;       // NM: matrix instructions per row tile
+    const int r31 = lane & 31, h = lane >> 5, x = lane & 15;
+    f32x16 nseed[MLP_NS];
+    const int ns0 = nd.narrow ? 0 : wave, nss = nd.narrow ? 1 : 4;
+    const WBase<> nb(nd.w, ns0, nss, lane);
+    const float neg = act_neg(d.act, d.slope);
+    const uint32_t lb = d.act == DHAUG_ACT_RELU ? 0u : 0x80008000u;
+    const int lep = r31 * (BUF01_PITCH * 2) | (((4 * wave) ^ x) << 4) | (h << 3);          // (see stack_layer)
+    typedef const unsigned char __attribute__((address_space(3))) * LdsPtr;
+    typedef unsigned char __attribute__((address_space(3))) * LdsWPtr;
+    uint32_t wa[4];
+    {
+        const uint32_t db = (uint32_t)(uintptr_t)(LdsPtr)buf_base(smem, d.dst);
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            wa[g] = db + (uint32_t)(lep ^ (g << 4));
+            asm volatile("" : "+v"(wa[g]));
+        }
+    }
+    f32x16 acc[2][MLP_NS];
+    auto pair_pack = [&](const f32x16 (&a)[MLP_NS], int j) -> uint32_t {
+        const int t = j >> 4, g = (j >> 2) & 3, e = j & 3;
+        const float v0 = a[t][4 * g + e], v1 = a[t][4 * g + e + 1];
+        if (!LEAKY)
+            return __builtin_bit_cast(uint32_t, __builtin_elementwise_max(__builtin_bit_cast(s16x2, pack_bf16x2(v0, v1)),
+                                                                          __builtin_bit_cast(s16x2, lb)));
+        return pack_bf16x2(act_fn(v0, neg), act_fn(v1, neg));
+    };
+    auto quad_store = [&](int mt, int j) {                                   // elements j .. j+3 of tile `mt`: one ds_write_b64
+        const int t = j >> 4, g = (j >> 2) & 3;
+        typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+        const u32x2 oo = {pair_pack(acc[mt & 1], j), pair_pack(acc[mt & 1], j + 2)};
+#ifdef ABL_NOWRITE
+        asm volatile("" :: "v"(oo));
+#else
+        *reinterpret_cast<u32x2 __attribute__((address_space(3)))*>((LdsWPtr)(uintptr_t)wa[g] + (t << 8) + mt * TILE_BYTES) = oo;
+#endif
+    };
+#pragma unroll
+    for (int mt = 0; mt < MLP_MT; ++mt) {
+#pragma unroll
+        for (int i = 0; i < NM; ++i) {                                       // i = 2 k + t
+            const int k = i / MLP_NS, t = i % MLP_NS;
+            acc[mt & 1][t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wl[t][k], gx[mt][k], k == 0 ? seed[t] : acc[mt & 1][t], 0, 0, 0);
+            __builtin_amdgcn_sched_barrier(0);
+            if (mt == MLP_MT - 1 && i == 0) load_seed(nd.bias, ns0, nss, lane, nseed);
+#ifndef ABL_NOWLOAD
+            if (mt == 1 || mt == 2) {
+#pragma unroll
+                for (int f = 0; f < 16; ++f) {                               // fragments [16 i / NM, 16 (i + 1) / NM) of the half
+                    if (f < 16 * i / NM || f >= 16 * (i + 1) / NM) continue;
+                    if (mt == 1) nlo[f >> 3][f & 7] = nb.frag(f >> 3, f & 7);
+                    else whi[f >> 3][f & 7] = nb.frag(f >> 3, 8 + (f & 7));
+                }
+            }
+#endif
+            if (mt > 0) {
+#pragma unroll
+                for (int q = 0; q < 8; ++q)                                  // quads [8 i / NM, 8 (i + 1) / NM) of the previous tile
+                    if (q >= 8 * i / NM && q < 8 * (i + 1) / NM) quad_store(mt - 1, 4 * q);
+            }
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        DHAUG_LSTAMP(dbg + 1 + mt)
+        DHAUG_BB_SPLIT()
+    }
+#pragma unroll
+    for (int q = 0; q < 8; ++q) quad_store(MLP_MT - 1, 4 * q);
+    DHAUG_LSTAMP(dbg + 5)
+#pragma unroll
+    for (int t = 0; t < MLP_NS; ++t) seed[t] = nseed[t];
+}
+
+// operand, bias, weights -- in this order -- then the layer
+template <bool LEAKY, int KS>
+__device__ __forceinline__ void lead_from_global(UnitPtr gl, const StackDesc& ld, const StackDesc& cur, unsigned char* smem, int wave,
+                                                 int lane, long long m0, long long M, WHalf& loA, WHalf& loB, WHalf& hi,
+                                                 f32x16 (&seed)[MLP_NS]) {
+    bf16x8 gx[MLP_MT][KS];
+    lead_operand<KS>(gl, m0, M, lane, gx);
+    load_seed(ld.bias, wave, 4, lane, seed);
+    const WBase<4> b(ld.w, wave, 4, lane);                                   // (the blob holds one whole chunk: 4 k-steps per slice)
+#pragma unroll
+    for (int t = 0; t < MLP_NS; ++t)
+#pragma unroll
+        for (int k = 0; k < KS; ++k) loB[t][k] = b.frag(t, k);
+    stack_lead_global<LEAKY, KS>(ld, cur, smem, wave, lane, gx, loB, loA, hi, seed, MLP_MAX_UNITS + 50);
+}
+
 // The network's output layer (N <= 64, K = 256) behind a stack: wave w computes rows [32w, 32w+32) for slices 0 and 1
 // with the fragments the last stack layer requested for it, and leaves act(.) as fp32 in the staging image
 // [128][OUT_PITCH] of buffer dst (store_output copies it out).
@@ -911,9 +1049,10 @@ __device__ __forceinline__ void save_image(int id, uint16_t* g, long long ld, in
 // ALT: the layers alternate (no residual, residual) -- the myResNet blocks -- and n is even
 // tail: 0 none, 1 the network's fp32 output layer (tail_layer), 2 a bf16 layer of <= 128 features (tail_gemm)
 // SAVE (forward-with-save): every run layer is followed by a barrier and the copy of its image to global memory
+// gl, gks: the bf16 LOAD whose tensor the lead reads from global memory in gks k-steps (PLAN_LEADG; inference only), gks = 0: none
 template <bool LEAKY, bool ALT, bool SAVE>
 __device__ __forceinline__ void gemm_stack(UnitPtr lead, int lead_ks, UnitPtr first, int n, int tail, unsigned char* smem,
-                                           int wave, int lane, long long m0, long long M, int tid) {
+                                           int wave, int lane, long long m0, long long M, int tid, UnitPtr gl = nullptr, int gks = 0) {
     // forward-with-save: layer j of the run writes the image of its producer `su` (the unit in front of it; none for the
     // first layer behind a LOAD) to that unit's save target -- a buffer resource over the tile's rows; zero records: nothing.
     // (The unit is read from the kernarg segment where it is needed, not carried in the layer descriptors.)
@@ -958,7 +1097,13 @@ __device__ __forceinline__ void gemm_stack(UnitPtr lead, int lead_ks, UnitPtr fi
     }
     int nold = 0;
     const __amdgpu_buffer_rsrc_t nosv = save_of(first, false, nold);
-    if (lead_ks != 0) {
+    if (!SAVE && gks != 0) {
+        const StackDesc ld = stack_desc(lead);
+        if (gks == 2) lead_from_global<LEAKY, 2>(gl, ld, cur, smem, wave, lane, m0, M, loA, loB, hi, seed);
+        else lead_from_global<LEAKY, 3>(gl, ld, cur, smem, wave, lane, m0, M, loA, loB, hi, seed);
+        lds_barrier();
+        DHAUG_LSTAMP(MLP_MAX_UNITS + 56)
+    } else if (lead_ks != 0) {
         const StackDesc ld = stack_desc(lead);
         load_seed(ld.bias, wave, 4, lane, seed);
         if (lead_ks == 8) {
@@ -1299,6 +1444,9 @@ __global__ __launch_bounds__(MLP_THREADS, 1) void fused_mlp_kernel(Program prog,
             int ni = i + 1;
             if (kind == U_GEMM && (plan & PLAN_STACK)) ni = i + ((plan & 15) != 0) + ((plan >> 4) & 63) + ((plan & (PLAN_TAIL | PLAN_TAIL_BF16)) ? 1 : 0);
             if (kind == U_GEMM && (plan & PLAN_PAIR)) ni = i + 2;
+            // a bf16 LOAD that runs as one unit with the stack behind it (the forward-with-save instantiation never gets the plan)
+            const bool leadg = !SAVE && kind == U_LOAD_BF16 && (plan & PLAN_LEADG);
+            if (leadg) ni = i + 2 + ((plan >> 4) & 63) + ((plan & (PLAN_TAIL | PLAN_TAIL_BF16)) ? 1 : 0);
             {
                 UnitPtr nu = units + (ni < nunits ? ni : 0);
                 hk = nu->kind;
@@ -1309,7 +1457,7 @@ __global__ __launch_bounds__(MLP_THREADS, 1) void fused_mlp_kernel(Program prog,
             const int ui = i;
             i = ni;
             (void)ui;
-            if (kind != U_GEMM) {
+            if (kind != U_GEMM && !leadg) {
                 // a STORE is not waited for where it is issued (lds_barrier orders only its LDS reads); the LOAD that
                 // reads the parked rows back drains the workgroup's stores first
                 if (kind == U_LOAD_BF16 && (plan & 1)) __syncthreads();      // only in programs that park rows with a STORE
@@ -1322,12 +1470,12 @@ __global__ __launch_bounds__(MLP_THREADS, 1) void fused_mlp_kernel(Program prog,
                 if (plan & PLAN_STACK) {
                     // a run of consecutive plain 256 -> 256 layers, possibly fed by this (narrow) layer and followed by
                     // the output layer
-                    const int lead_ks = plan & 15, run = (plan >> 4) & 63;
+                    const int gks = leadg ? (plan & 15) : 0, lead_ks = leadg ? 4 : (plan & 15), run = (plan >> 4) & 63;
                     const int tail = (plan & PLAN_TAIL) ? 1 : ((plan & PLAN_TAIL_BF16) ? 2 : 0);
-                    UnitPtr f0 = u + (lead_ks != 0), tu = f0 + run;
-                    if ((plan & PLAN_LEAKY) || NAN_SAFE_TU) gemm_stack<true, false, SAVE>(u, lead_ks, f0, run, tail, smem, wave, lane, m0, M, tid);
-                    else if (plan & PLAN_ALT) gemm_stack<false, true, SAVE>(u, lead_ks, f0, run, tail, smem, wave, lane, m0, M, tid);
-                    else gemm_stack<false, false, SAVE>(u, lead_ks, f0, run, tail, smem, wave, lane, m0, M, tid);
+                    UnitPtr lu = u + (leadg ? 1 : 0), f0 = lu + (lead_ks != 0), tu = f0 + run;
+                    if ((plan & PLAN_LEAKY) || NAN_SAFE_TU) gemm_stack<true, false, SAVE>(lu, lead_ks, f0, run, tail, smem, wave, lane, m0, M, tid, u, gks);
+                    else if (plan & PLAN_ALT) gemm_stack<false, true, SAVE>(lu, lead_ks, f0, run, tail, smem, wave, lane, m0, M, tid, u, gks);
+                    else gemm_stack<false, false, SAVE>(lu, lead_ks, f0, run, tail, smem, wave, lane, m0, M, tid, u, gks);
                     lds_barrier();
                     if (SAVE) {                                              // (inside the run every layer saved its input)
                         UnitPtr lu = tu - 1;                                 // the run's last layer: nobody in the run read its image
@@ -1470,7 +1618,9 @@ __global__ __launch_bounds__(256) void pack_wfrag_desc_kernel(const dhaug_wfrag_
 
 // how unit i is executed (see the dispatch in fused_mlp_kernel): a run of >= min_run full-width 256 -> 256 layers goes to
 // gemm_stack, together with the narrow layer (K <= 128) feeding it and the <= 64-wide fp32 output layer behind it
-int plan_unit(const Program& p, int i) {
+// leadg: may a bf16 LOAD and the stack behind it become one dispatch whose lead layer reads the tensor from global memory
+// (PLAN_LEADG)?  Inference launches only; DHAUG_MLP_NOLEADG in the environment turns the route off (A/B runs, tests).
+int plan_unit(const Program& p, int i, bool leadg = false) {
     const Unit* U = p.u;
     const Unit& u = U[i];
     if (u.kind != U_GEMM) {
@@ -1478,7 +1628,27 @@ int plan_unit(const Program& p, int i) {
         // stores first (full barrier); programs without a STORE skip that wait for write acknowledgements
         int parks = 0;
         for (int j = 0; j < p.nunits; ++j) parks |= U[j].kind == U_STORE_BF16;
-        return u.kind == U_LOAD_BF16 ? parks : 0;
+        if (u.kind != U_LOAD_BF16) return 0;
+        // The LOAD feeds nothing but the lead layer of a stack: 32 or 48 columns (16-byte rows and base: checked by the caller), the
+        // next unit a lead of one chunk (no second source, no residual: plan_unit) that reads this image, and NO other reader of the
+        // image -- it is not written any more -- before buffer dst is written whole again, by a layer of the run (all 256 columns)
+        // or by a LOAD.  A unit's own reads come before its write: an in-place residual of the first run layer is a reader.
+        // Programs that park rows keep the LOAD (it needs the full barrier first).
+        if (!leadg || parks || getenv("DHAUG_MLP_NOLEADG") || (u.cols != 32 && u.cols != 48) || u.ld > (1 << 20) || i + 1 >= p.nunits)
+            return parks;
+        const Unit& l = U[i + 1];
+        if (l.kind != U_GEMM || l.src != u.dst) return parks;
+        const int sp = plan_unit(p, i + 1);
+        if (!(sp & PLAN_STACK) || (sp & 15) != 4) return parks;
+        const int b = u.dst, run_end = i + 2 + ((sp >> 4) & 63);                 // run layers: units [i + 2, run_end)
+        for (int j = i + 2; j < p.nunits; ++j) {
+            const Unit& v = U[j];
+            if (v.kind == U_STORE_BF16 ? v.src == b
+                                       : (v.kind == U_GEMM && (v.src == b || (v.ksteps2 > 0 && v.src2 == b) || v.res == b)))
+                return parks;
+            if (v.dst == b && (v.kind != U_GEMM || j < run_end)) break;
+        }
+        return (sp & ~15) | (u.cols >> 4) | PLAN_LEADG;
     }
     const bool wide = u.ksteps2 == 0 && u.N > 224 && !(u.flags & (F_OUT_F32 | F_DOT_OUT)) && u.src < 2 && u.dst < 2;
     const int ks4 = (u.ksteps + 3) & ~3;                                 // the fragment blob and the LOAD pad to whole chunks
@@ -1562,14 +1732,15 @@ int dhaug_pack_wfrag_composed(const float* Wa, int64_t ldwa, const float* bias_a
     return dhaug_launch_status();
 }
 
-int dhaug_mlp_forward(const dhaug_mlp_unit* units, int nunits, int64_t M, void* stream) {
+}  // extern "C"
+
+// validation and planning of a program: everything dhaug_mlp_forward does in front of the launch
+static int mlp_prepare(const dhaug_mlp_unit* units, int nunits, int64_t M, Program& prog, bool& any_save) {
     DHAUG_CHECK(nunits >= 1 && nunits <= MLP_MAX_UNITS && M >= 0, DHAUG_EINVAL);
     DHAUG_CHECK_PTR(units);
-    if (M == 0) return DHAUG_OK;
-    Program prog;
     prog.nunits = nunits;
     prog.min_run = getenv("DHAUG_MLP_NOSTACK") ? 1 << 20 : 2;                // debugging aid: layer-at-a-time path only
-    bool any_save = false;
+    any_save = false;
     for (int i = 0; i < nunits; ++i) {
         const dhaug_mlp_unit& s = units[i];
         Unit& u = prog.u[i];
@@ -1632,7 +1803,8 @@ int dhaug_mlp_forward(const dhaug_mlp_unit* units, int nunits, int64_t M, void* 
             DHAUG_CHECK(u.kind == U_LOAD_F32 ? (u.ld % 4 == 0) : (u.ld % 8 == 0), DHAUG_EALIGN);
         }
     }
-    for (int i = 0; i < prog.nunits; ++i) prog.u[i].plan = plan_unit(prog, i);
+    // (forward-with-save keeps its LOADs: fused_mlp_kernel<true> and its schedule are what they were)
+    for (int i = 0; i < prog.nunits; ++i) prog.u[i].plan = plan_unit(prog, i, !any_save);
     {   // sign bits are written by the layers of a run and by the narrow layer feeding it (not by layer-at-a-time units)
         bool in_run[MLP_MAX_UNITS] = {};
         for (int i = 0; i < prog.nunits;) {
@@ -1647,6 +1819,27 @@ int dhaug_mlp_forward(const dhaug_mlp_unit* units, int nunits, int64_t M, void* 
         }
         for (int i = 0; i < prog.nunits; ++i) DHAUG_CHECK(prog.u[i].bits == nullptr || in_run[i], DHAUG_EUNSUPPORTED);
     }
+    return DHAUG_OK;
+}
+
+extern "C" {
+
+int dhaug_mlp_plan(const dhaug_mlp_unit* units, int nunits, int64_t M, int32_t* plans_out) {
+    DHAUG_CHECK_PTR(plans_out);
+    Program prog;
+    bool any_save;
+    if (const int rc = mlp_prepare(units, nunits, M, prog, any_save)) return rc;
+    for (int i = 0; i < nunits; ++i) plans_out[i] = prog.u[i].plan;
+    return DHAUG_OK;
+}
+
+int dhaug_mlp_forward(const dhaug_mlp_unit* units, int nunits, int64_t M, void* stream) {
+    DHAUG_CHECK(nunits >= 1 && nunits <= MLP_MAX_UNITS && M >= 0, DHAUG_EINVAL);
+    DHAUG_CHECK_PTR(units);
+    if (M == 0) return DHAUG_OK;                                             // an empty batch is a no-op that looks at no unit
+    Program prog;
+    bool any_save;
+    if (const int rc = mlp_prepare(units, nunits, M, prog, any_save)) return rc;
     const long long ntiles = (M + MLP_BM - 1) / MLP_BM;
     const unsigned grid = dhaug_persistent_grid(ntiles);           // one persistent workgroup per CU
     // forward-with-save (a unit asks for its image in global memory) is a second instantiation: the inference kernel's

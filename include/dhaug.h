@@ -679,6 +679,15 @@ int dhaug_pack_wfrag_composed(const float* Wa, int64_t ldwa, const float* bias_a
  * dhaug_pack_wfrag_composed). */
 int dhaug_mlp_forward(const dhaug_mlp_unit* units, int nunits, int64_t M, void* stream);
 
+/* Host only, launches nothing: the validation of dhaug_mlp_forward and its planning pass over the same program; plans_out[i]
+ * receives how unit i would be executed (an internal encoding, stable enough for tests: bit 13 = a run of full-width layers,
+ * DHAUG_MLP_PLAN_LEADG on a bf16 LOAD = the LOAD and the stack behind it run as one unit whose lead layer reads the tensor
+ * from global memory instead of an LDS image).  No pointer of the program is dereferenced.  Returns what dhaug_mlp_forward
+ * would return in front of its launch. */
+#define DHAUG_MLP_PLAN_STACK  (1 << 13)
+#define DHAUG_MLP_PLAN_LEADG  (1 << 15)
+int dhaug_mlp_plan(const dhaug_mlp_unit* units, int nunits, int64_t M, int32_t* plans_out);
+
 /* Parity-grade variant of the same programs: every operand is an fp16 pair x = hi + lo (22 mantissa bits), a product is
  * Whi Xhi + Whi Xlo + Wlo Xhi on v_mfma_f32_32x32x16_f16 with fp32 accumulation -- fp32-grade results (the reference's
  * layers are fp32 nn.Linear: R/models_Fk_GAN/Fk_discriminator.py:180-201,253-266, R/models_Fk_GAN/Fk_generator.py:115-119;

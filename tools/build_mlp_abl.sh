@@ -11,7 +11,8 @@ VARIANTS=${VARIANTS:-"base: vform:-mllvm,-amdgpu-mfma-vgpr-form=1"}
 for v in $VARIANTS; do
   n=${v%%:*}; d=${v#*:}; d=${d//,/ }; d=${d//@/ }
   /opt/rocm/bin/hipcc $F $d -c $P/csrc/dhaug_mlp.hip -o $O/mlp_$n.o &
-  /opt/rocm/bin/hipcc $F ${d//-DDHAUG_MLP_TIMING/} -c $P/csrc/dhaug_mlp_save.hip -o $O/mlp_save_$n.o &      # (the stamps are the inference unit's)
+  ds=${d//-DDHAUG_MLP_TIMING_UNITS/}
+  /opt/rocm/bin/hipcc $F ${ds//-DDHAUG_MLP_TIMING/} -c $P/csrc/dhaug_mlp_save.hip -o $O/mlp_save_$n.o &      # (the stamps are the inference unit's)
 done
 wait
 for v in $VARIANTS; do

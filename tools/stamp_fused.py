@@ -17,8 +17,16 @@ z = torch.randn(B, 128, device="cuda"); x3 = torch.randn(B, 16, 3, device="cuda"
 L = _lib.lib()
 N = 6 * 32 + 69
 buf = (ctypes.c_longlong * N)()
+# STAMP_CRITICS=1: only the forward's critics launch (both critics in one program, bf16 inputs as Fk_Generator.sample_for_critics
+# hands them over): a stack whose lead reads its operand from global memory shows as ONE unit under its LOAD's index, the lead's
+# own index stays empty.  (One launch kind per process: the stamp array is never cleared.)
+x3b, x2b = x3.reshape(B, 48).to(torch.bfloat16), x2.reshape(B, 32).to(torch.bfloat16)
+kcs = torch.randn(B, 32, device="cuda").to(torch.bfloat16)
+RUNS = (("G", lambda: fused.generator_head(G, z)), ("D3", lambda: fused.critic3d(D3, x3)), ("D2", lambda: fused.critic2d(D2, x2)), ("D3", lambda: fused.critic3d(D3, x3)))
+if os.environ.get("STAMP_CRITICS"):
+    RUNS = (("critics", lambda: fused.critics(D3, D2, x3b, kcs, x2b)),)
 with torch.no_grad():
-    for name, fn in (("G", lambda: fused.generator_head(G, z)), ("D3", lambda: fused.critic3d(D3, x3)), ("D2", lambda: fused.critic2d(D2, x2)), ("D3", lambda: fused.critic3d(D3, x3))):
+    for name, fn in RUNS:
         for _ in range(3): fn()
         torch.cuda.synchronize()
         L.dhaug_debug_mlp_stamps(buf, N)
