@@ -34,6 +34,7 @@ SIGNATURES = {
     "dhaug_pose_metrics": [_vp, _vp, _i64, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp],
     "dhaug_pair_batch": [_vp, _vp, _i64, _i32, _i32, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "dhaug_pose_mse": [_vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp],
+    "dhaug_pose_mpjpe": [_vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp],
     "dhaug_grad_sumsq": [_vp, _i64, _f32, _vp, _vp, _vp],
     "dhaug_adam_clip_step": [_vp, _vp, _vp, _vp, _i64, _f32, _f32, _f32, _f32, _vp, _f32, _f32, _vp, _vp, _vp],
     "dhaug_gemm_bf16_dmask": [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _i32, _f32, _vp, _i64, _i64, _i64, _i64, _vp],

@@ -9,6 +9,15 @@
 //  dhaug_pose_mse       launch 1: grad = (pred - tgt) * fl32(2 / numel), squares summed in fp64 per workgroup (butterfly over
 //                       the wave, the four waves in order) -> one partial each; launch 2 (one wave): the partials in index order
 //                       -> loss (rounded to fp32 once) and the meter record.
+//  dhaug_pose_mpjpe     mean(norm(pred - tgt, dim=-1)) (R/utils/loss.py:8-14) forward + backward with the same two launches.
+//                       Launch 1, per joint: d = pred - tgt in fp64 (exact), e = sqrt(dx^2 + dy^2 + dz^2) in fp64,
+//                       grad = fl32(d / (e * joints)) -- rounded once -- and exactly 0 where e == 0 (the zero subgradient torch's
+//                       autograd gives there); e summed in fp64 per workgroup as above.  Four joints per lane = three float4 loads
+//                       per tensor; a scalar path for the joints % 4 tail and for bases off a 16-byte boundary.  Launch 2 is
+//                       dhaug_pose_mse's: loss = fl32(sum / joints) and the meter record.
+//                       A NaN input gives a NaN loss and a NaN gradient for that joint only.  Not reproduced: the fp32 overflow
+//                       of the reference's squares (|d| >~ 1.8e19 gives an inf loss there; here the distance is formed in fp64),
+//                       and its zero gradient for a distance too small for fp32 squares (here: the true unit vector / joints).
 //  dhaug_grad_sumsq     per-workgroup fp64 partials of (g * grad_scale)^2 over a partition fixed by n (and the pointer's
 //                       alignment); one thread also advances the optimizer's step count (the Adam launch behind it reads it:
 //                       stream order is the synchronisation).
@@ -25,7 +34,7 @@ namespace {
 
 constexpr int kBlock = 256;
 constexpr int kPairBlock = 64;                                  // one pose-frame per lane: small workgroups spread a 1 024-pose batch
-constexpr int kMaxGrid = 2048;                                  // partials of dhaug_pose_mse
+constexpr int kMaxGrid = 2048;                                  // partials of dhaug_pose_mse / dhaug_pose_mpjpe
 constexpr int kSumsqMaxGrid = DHAUG_GRAD_SUMSQ_MAX_PARTIALS;    // partials of dhaug_grad_sumsq: every Adam workgroup re-adds them
 
 __device__ __forceinline__ double wave_sum(double v) {
@@ -116,7 +125,7 @@ __global__ __launch_bounds__(kBlock) void pose_mse_kernel(const float* __restric
     if (threadIdx.x == 0) partials[blockIdx.x] = acc;
 }
 
-// one wave: loss = fl32(sum / numel); the meter takes what AverageMeter.update(loss.item(), poses) adds
+// one wave: loss = fl32(sum / n), n = numel (MSE) or joints (MPJPE); the meter takes what AverageMeter.update(loss.item(), poses) adds
 __global__ __launch_bounds__(64) void pose_mse_finish_kernel(const double* __restrict__ partials, int nparts, long long n,
                                                              long long poses, float* __restrict__ loss,
                                                              dhaug_loss_meter* __restrict__ meter) {
@@ -132,6 +141,49 @@ __global__ __launch_bounds__(64) void pose_mse_finish_kernel(const double* __res
             meter->steps += 1;
         }
     }
+}
+
+// ---------------------------------------------------------------------------------------------------------------- MPJPE
+// one joint: its distance (fp64), and d / (e * joints) rounded to fp32 once -- 0 where the distance is 0, NaN where it is NaN
+__device__ __forceinline__ double mpjpe_joint(double dx, double dy, double dz, double joints, float& gx, float& gy, float& gz) {
+    const double e = sqrt(dx * dx + dy * dy + dz * dz);
+    const double den = e * joints;
+    const bool zero = e == 0.0;
+    gx = zero ? 0.0f : (float)(dx / den);
+    gy = zero ? 0.0f : (float)(dy / den);
+    gz = zero ? 0.0f : (float)(dz / den);
+    return e;
+}
+
+__global__ __launch_bounds__(kBlock) void pose_mpjpe_kernel(const float* __restrict__ pred, const float* __restrict__ tgt,
+                                                            float* __restrict__ grad, long long joints, int vec,
+                                                            double* __restrict__ partials) {
+    __shared__ double lds[4];
+    double acc = 0.0;
+    const double nj = (double)joints;
+    const long long tid = (long long)blockIdx.x * kBlock + threadIdx.x, stride = (long long)gridDim.x * kBlock;
+    const long long n4 = vec ? joints >> 2 : 0;                  // groups of four joints = 12 floats = three float4
+    for (long long i = tid; i < n4; i += stride) {
+        const float4* p4 = reinterpret_cast<const float4*>(pred) + 3 * i;
+        const float4* t4 = reinterpret_cast<const float4*>(tgt) + 3 * i;
+        const float4 p0 = p4[0], p1 = p4[1], p2 = p4[2], t0 = t4[0], t1 = t4[1], t2 = t4[2];
+        float4 g0, g1, g2;
+        acc += mpjpe_joint((double)p0.x - (double)t0.x, (double)p0.y - (double)t0.y, (double)p0.z - (double)t0.z, nj, g0.x, g0.y, g0.z);
+        acc += mpjpe_joint((double)p0.w - (double)t0.w, (double)p1.x - (double)t1.x, (double)p1.y - (double)t1.y, nj, g0.w, g1.x, g1.y);
+        acc += mpjpe_joint((double)p1.z - (double)t1.z, (double)p1.w - (double)t1.w, (double)p2.x - (double)t2.x, nj, g1.z, g1.w, g2.x);
+        acc += mpjpe_joint((double)p2.y - (double)t2.y, (double)p2.z - (double)t2.z, (double)p2.w - (double)t2.w, nj, g2.y, g2.z, g2.w);
+        float4* o4 = reinterpret_cast<float4*>(grad) + 3 * i;
+        o4[0] = g0; o4[1] = g1; o4[2] = g2;
+    }
+    for (long long j = 4 * n4 + tid; j < joints; j += stride) {
+        const float* p = pred + 3 * j;
+        const float* t = tgt + 3 * j;
+        float gx, gy, gz;
+        acc += mpjpe_joint((double)p[0] - (double)t[0], (double)p[1] - (double)t[1], (double)p[2] - (double)t[2], nj, gx, gy, gz);
+        grad[3 * j] = gx; grad[3 * j + 1] = gy; grad[3 * j + 2] = gz;
+    }
+    acc = block_sum(acc, lds);
+    if (threadIdx.x == 0) partials[blockIdx.x] = acc;
 }
 
 // ------------------------------------------------------------------------------------------------- gradient norm + Adam
@@ -285,6 +337,25 @@ extern "C" int dhaug_pose_mse(const float* pred, const float* tgt, int64_t numel
     hipLaunchKernelGGL(pose_mse_kernel, dim3(grid), dim3(kBlock), 0, s, pred, tgt, grad, (long long)numel,
                        (float)(2.0 / (double)numel), vec, partials);
     hipLaunchKernelGGL(pose_mse_finish_kernel, dim3(1), dim3(64), 0, s, (const double*)partials, grid, (long long)numel,
+                       (long long)poses, loss, reinterpret_cast<dhaug_loss_meter*>(meter));
+    return dhaug_launch_status();
+}
+
+extern "C" int dhaug_pose_mpjpe(const float* pred, const float* tgt, int64_t joints, int64_t poses, float* grad, float* loss,
+                                void* meter, void* workspace, void* stream) {
+    DHAUG_CHECK(joints >= 0 && poses >= 0, DHAUG_EINVAL);
+    DHAUG_CHECK(grad != nullptr && loss != nullptr && workspace != nullptr, DHAUG_EINVAL);
+    if (joints == 0) return DHAUG_OK;
+    DHAUG_CHECK_PTR(pred); DHAUG_CHECK_PTR(tgt);
+    DHAUG_CHECK((reinterpret_cast<uintptr_t>(pred) | reinterpret_cast<uintptr_t>(tgt) | reinterpret_cast<uintptr_t>(grad) |
+                 reinterpret_cast<uintptr_t>(loss)) % 4 == 0, DHAUG_EALIGN);
+    DHAUG_CHECK((reinterpret_cast<uintptr_t>(workspace) | reinterpret_cast<uintptr_t>(meter)) % 8 == 0, DHAUG_EALIGN);
+    const int vec = dhaug_aligned16(pred) && dhaug_aligned16(tgt) && dhaug_aligned16(grad);
+    const int grid = dhaug_stream_grid((joints + 3) / 4, kBlock, kMaxGrid);
+    const hipStream_t s = (hipStream_t)stream;
+    double* partials = reinterpret_cast<double*>(workspace);
+    hipLaunchKernelGGL(pose_mpjpe_kernel, dim3(grid), dim3(kBlock), 0, s, pred, tgt, grad, (long long)joints, vec, partials);
+    hipLaunchKernelGGL(pose_mse_finish_kernel, dim3(1), dim3(64), 0, s, (const double*)partials, grid, (long long)joints,
                        (long long)poses, loss, reinterpret_cast<dhaug_loss_meter*>(meter));
     return dhaug_launch_status();
 }

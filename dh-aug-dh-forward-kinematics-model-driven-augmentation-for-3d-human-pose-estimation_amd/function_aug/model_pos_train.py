@@ -7,6 +7,7 @@ The posenet is whatever nn.Module the caller passes; what runs in this package's
     upload);
   * nn.MSELoss(reduction='mean'): dhaug_pose_mse gives the loss, its gradient (the loop calls outputs.backward(grad)) and the
     epoch's loss meter, AverageMeter.update(loss, num_poses) on the device;
+  * utils.loss.mpjpe of this package (the criterion of the reference's video command): dhaug_pose_mpjpe, the same way;
   * nn.utils.clip_grad_norm_(max_norm=1) + optimizer.step(): optimizer.clip_step(1) of optim.PosenetAdam, two launches.
 Each piece falls back on its own to what the reference calls (criterion(...).backward(), clip_grad_norm_, optimizer.step() of a
 stock torch optimizer) when it does not apply; the loss still goes to the meter on the device.  Nothing is read on the host per
@@ -18,6 +19,7 @@ import torch.nn as nn
 
 from .. import ops
 from ..optim import PosenetAdam
+from ..utils.loss import mpjpe
 
 METERS = ("loss", "flip_loss", "back_loss", "back_flip_loss")
 _TRACE_CHUNK = 1024
@@ -47,7 +49,12 @@ class StepRunner:
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise RuntimeError("the posenet training loops need a GPU (no CPU fallback exists)")
-        self.fused_loss = isinstance(criterion, nn.MSELoss) and criterion.reduction == "mean"
+        # the fused criteria: nn.MSELoss(reduction='mean') and this package's mpjpe; any other callable is called as it is
+        self.fused_loss = None
+        if isinstance(criterion, nn.MSELoss) and criterion.reduction == "mean":
+            self.fused_loss = ops.pose_mse
+        elif criterion is mpjpe:
+            self.fused_loss = ops.pose_mpjpe
         self.fused_opt = hasattr(optimizer, "clip_step")
         self.meters = ops.loss_meters(len(METERS), self.device)
         self.workspace = ops.posetrain_workspace(self.device)
@@ -67,10 +74,10 @@ class StepRunner:
         rec = None if meter is None else self.meters[METERS.index(meter)]
         outputs = self.model(inputs)
         self.opt.zero_grad()
-        if self.fused_loss:
+        if self.fused_loss is not None:
             if tuple(outputs.shape) != tuple(targets.shape):
                 raise ValueError("posenet output %s and target %s differ in shape" % (tuple(outputs.shape), tuple(targets.shape)))
-            _, grad = ops.pose_mse(outputs, targets, num_poses, meter=rec, workspace=self.workspace, loss=loss_slot)
+            _, grad = self.fused_loss(outputs, targets, num_poses, meter=rec, workspace=self.workspace, loss=loss_slot)
             outputs.backward(grad.view(outputs.shape))
         else:
             loss = self.criterion(outputs, targets)

@@ -368,7 +368,7 @@ def center_flip(x, center, flip, adjoint=False):
 
 # ---------------------------------------------------------------------------------------------- posenet training
 def posetrain_workspace(device=None):
-    """the partials' workspace of pose_mse / grad_sumsq / adam_clip_step (one call chain at a time per workspace)"""
+    """the partials' workspace of pose_mse / pose_mpjpe / grad_sumsq / adam_clip_step (one call chain at a time per workspace)"""
     return torch.empty(_lib.POSETRAIN_WORKSPACE_BYTES // 8, dtype=torch.int64, device=device if device is not None else "cuda")
 
 
@@ -440,6 +440,31 @@ def pose_mse(pred, target, poses, meter=None, workspace=None, loss=None):
         loss = torch.empty(1, dtype=torch.float32, device=dev)
     assert loss.is_cuda and loss.dtype == torch.float32 and loss.numel() == 1
     _lib.call("dhaug_pose_mse", _p(y), _p(x), y.numel(), int(poses), _p(grad), _p(loss), _p(meter), _p(ws), _stream())
+    return loss, grad
+
+
+def pose_mpjpe(pred, target, poses, meter=None, workspace=None, loss=None):
+    """mpjpe = mean(norm(pred - target, dim=-1)) forward + backward (dhaug_pose_mpjpe) over (..., 3) rows: returns (loss, grad)
+    with pose_mse's conventions -- loss a 1-element fp32 device tensor (or the one given), grad = d loss / d pred in pred's
+    shape (exactly 0 for a joint at distance 0), meter one record of loss_meters()."""
+    if tuple(pred.shape) != tuple(target.shape):
+        raise ValueError("pose_mpjpe: pred %s and target %s differ in shape" % (tuple(pred.shape), tuple(target.shape)))
+    if pred.dim() < 1 or pred.shape[-1] != 3:
+        raise ValueError("pose_mpjpe: the last dimension must be 3, got %s" % (tuple(pred.shape),))
+    if int(poses) < 0:
+        raise ValueError("pose_mpjpe: poses must be >= 0")
+    y = _dev(pred.detach(), torch.float32, "pose_mpjpe")
+    x = _dev(target.detach(), torch.float32, "pose_mpjpe")
+    dev = y.device
+    if meter is not None:
+        assert meter.is_cuda and meter.dtype == torch.int64 and meter.numel() == _lib.LOSS_METER_WORDS and meter.is_contiguous(), \
+            "pose_mpjpe: meter must be one record of loss_meters()"
+    ws = workspace if workspace is not None else posetrain_workspace(dev)
+    grad = torch.empty_like(y)
+    if loss is None:
+        loss = torch.empty(1, dtype=torch.float32, device=dev)
+    assert loss.is_cuda and loss.dtype == torch.float32 and loss.numel() == 1
+    _lib.call("dhaug_pose_mpjpe", _p(y), _p(x), y.numel() // 3, int(poses), _p(grad), _p(loss), _p(meter), _p(ws), _stream())
     return loss, grad
 
 

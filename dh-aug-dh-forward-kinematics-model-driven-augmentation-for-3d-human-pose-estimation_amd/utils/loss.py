@@ -1,5 +1,6 @@
 """Drop-ins for the evaluation metrics of R/utils/loss.py (mpjpe :8-14, p_mpjpe :123-164, compute_PCK / compute_AUC :192-225),
-computed on the device by one dhaug_pose_metrics launch (plus its one-wave reduction).
+computed on the device by one dhaug_pose_metrics launch (plus its one-wave reduction).  mpjpe is also the criterion of the
+reference's video command: called on a device tensor that requires grad it is differentiable (dhaug_pose_mpjpe).
 
 Same signatures and return values as the reference for host (numpy / CPU tensor) inputs: they are uploaded, and one host
 read returns what the reference returns (a CPU 0-d tensor for mpjpe, a numpy scalar for p_mpjpe, a float for compute_PCK,
@@ -54,9 +55,31 @@ def _f64(tot):
     return tot[:2].view(torch.float64)
 
 
+class _MpjpeFn(torch.autograd.Function):
+    """mpjpe as a training criterion: ops.pose_mpjpe gives the loss and d loss / d predicted in one launch pair; the gradient is
+    kept for the backward.  First order only."""
+
+    @staticmethod
+    def forward(ctx, predicted, target):
+        loss, grad = ops.pose_mpjpe(predicted, target, predicted.numel() // 48)
+        ctx.save_for_backward(grad)
+        return loss.reshape(())
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_output):
+        (grad,) = ctx.saved_tensors
+        g = grad_output * grad
+        return g, (-g if ctx.needs_input_grad[1] else None)
+
+
 def mpjpe(predicted, target):
-    """mean per-joint position error (Protocol #1), the mean of the fp32 joint distances"""
+    """mean per-joint position error (Protocol #1).  As a metric (no gradient asked for, or host inputs): the mean of the fp32
+    joint distances from dhaug_pose_metrics.  As a criterion -- an fp32 device tensor that requires grad, with gradients enabled
+    -- a 0-d tensor with a grad_fn over dhaug_pose_mpjpe (fp64 distances; a joint at distance 0 gets a zero gradient)."""
     y, x, host = _device_pair(predicted, target, "mpjpe")
+    if not host and predicted.dtype == torch.float32 and predicted.requires_grad and torch.is_grad_enabled():
+        return _MpjpeFn.apply(y, x.to(torch.float32))
     tot = _totals(y, x)
     v = _f64(tot)[0] / (16.0 * tot[2].double())
     dtype = predicted.dtype if torch.is_tensor(predicted) else torch.float32

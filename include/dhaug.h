@@ -285,6 +285,18 @@ int dhaug_pose_metrics(const float* pred, const float* target, int64_t P, int ce
  *   (stream order).  Per-workgroup partials added in a fixed order, no atomics: the same call sequence gives the same bits.
  *   DHAUG_EINVAL: numel or poses < 0, NULL grad / loss / workspace, (numel > 0) NULL pred / tgt.  numel = 0 is a no-op.
  *
+ * dhaug_pose_mpjpe: mpjpe of R/utils/loss.py:8-14, torch.mean(torch.norm(pred - tgt, dim=-1)), forward and backward of joints rows
+ *   of 3 contiguous fp32 values, the same two launches.  Per joint d = pred - tgt and e = sqrt(dx^2 + dy^2 + dz^2) in fp64 (the
+ *   difference is exact); grad (joints x 3) = fl32(d / (e * joints)), rounded once, and exactly 0 in all three components where
+ *   e == 0 (torch's subgradient there); every element written.  *loss = fl32(sum of e / joints), the sum in fp64 in a fixed order;
+ *   meter, workspace, reproducibility and the one-call-per-workspace rule as dhaug_pose_mse.  pred, tgt, grad: 4-byte aligned;
+ *   16-byte aligned bases take the float4 path (four joints per lane), others and the joints % 4 tail a scalar one -- the same
+ *   values.  A NaN input gives a NaN loss and a NaN gradient for that joint only.  NOT reproduced from the reference's fp32
+ *   arithmetic: the overflow of its squares (|d| >~ 1.8e19 gives an inf loss there) and the zero gradient it returns for a distance
+ *   too small for fp32 squares (|d| <~ 1e-23: here the true unit vector over joints).
+ *   DHAUG_EINVAL: joints or poses < 0, NULL grad / loss / workspace, (joints > 0) NULL pred / tgt; DHAUG_EALIGN: meter or workspace
+ *   not 8-byte aligned.  joints = 0 is a no-op.
+ *
  * dhaug_grad_sumsq + dhaug_adam_clip_step: nn.utils.clip_grad_norm_(params, max_norm) (error_if_nonfinite=False) followed by
  *   torch.optim.Adam.step() on flat fp32 vectors of n elements, two launches.
  *   dhaug_grad_sumsq writes per-workgroup fp64 partial sums of (fl32(grad[i] * grad_scale))^2 into workspace (a partition fixed by
@@ -308,6 +320,8 @@ int dhaug_pair_batch(const float* p3, const float* p2, int64_t M, int F3, int F2
                      float* inp_flip_back, void* stream);
 int dhaug_pose_mse(const float* pred, const float* tgt, int64_t numel, int64_t poses, float* grad, float* loss, void* meter,
                    void* workspace, void* stream);
+int dhaug_pose_mpjpe(const float* pred, const float* tgt, int64_t joints, int64_t poses, float* grad, float* loss, void* meter,
+                     void* workspace, void* stream);
 int dhaug_grad_sumsq(const float* grad, int64_t n, float grad_scale, void* workspace, int* step_counter, void* stream);
 int dhaug_adam_clip_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, float lr, float beta1,
                          float beta2, float eps, const int* step_dev, float grad_scale, float max_norm, const void* workspace,
