@@ -85,6 +85,7 @@ SIGNATURES = {
     "dhaug_bn_act_backward": [_vp, _i32, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _f32, _u64, _u64, _vp, _vp, _i64, _vp, _i64, _vp,
                               _vp, _i64, _i64, _vp],
     "dhaug_bn_fold": [_vp, _i64, _vp, _vp, _vp, _vp, _f32, _vp, _i64, _vp, _vp, _i64, _i64, _vp],
+    "dhaug_bn_fold_bias": [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _f32, _vp, _i64, _vp, _vp, _i64, _i64, _vp],
     "dhaug_conv_taps_pack_bf16": [_vp, _i64, _i64, _i32, _vp, _i64, _vp, _i64, _vp],
     "dhaug_conv_taps_permute_f32": [_vp, _vp, _i64, _i64, _i32, _i32, _i32, _vp],
     "dhaug_tap_gather": [_vp, _i32, _i64, _i64, _i64, _i64, _i32, _i32, _i32, _vp, _i64, _vp, _i64, _vp],

@@ -12,6 +12,8 @@
 //  dhaug_bn_act_backward_partials  gz = g * keep / (1 - p) * [pre-activation > 0]: sum gz and sum gz * xhat per column and chunk, fp64.
 //  dhaug_bn_act_backward           dz = gamma * rstd * (gz - sum gz / M - xhat * sum(gz xhat) / M); chunk 0 writes dgamma, dbeta.
 //  dhaug_bn_fold                   W' = gamma * rstd_run (.) rows of W, b' = beta - running_mean * gamma * rstd_run.
+//  dhaug_bn_fold_bias              the same for a layer with a bias b of its own (R/models_baseline/mlp/linear_model.py: nn.Linear in
+//                                  front of every BatchNorm): b' = beta + (b - running_mean) * gamma * rstd_run.
 //
 // No mask is stored: the backward kernels recompute the pre-activation with the forward kernel's own function (bn_pre, below: one
 // rounding sequence, nothing for the compiler to contract differently) and regenerate the keep decision from (seed, offset).
@@ -441,23 +443,45 @@ __global__ __launch_bounds__(kBlock) void bn_act_backward_kernel(BwdArgs a) {
     }
 }
 
+// W' = gamma * rstd_run (.) rows of W, the part the two fold kernels share.  One rounding per result: the scale gamma * rstd_run stays
+// in fp64 until the product is formed
+__device__ __forceinline__ void fold_weight(const float* __restrict__ W, long long ldw, const float* __restrict__ gamma,
+                                            const float* __restrict__ rvar, float eps, float* __restrict__ Wout, long long ld_out,
+                                            long long N, long long K, long long tid, long long stride) {
+    for (long long i = tid; i < N * K; i += stride) {
+        const long long n = i / K, k = i - n * K;
+        const double sc = (double)gamma[n] / sqrt((double)rvar[n] + (double)eps);
+        Wout[n * ld_out + k] = (float)(sc * (double)W[n * ldw + k]);
+    }
+}
+
 __global__ __launch_bounds__(kBlock) void bn_fold_kernel(const float* __restrict__ W, long long ldw, const float* __restrict__ gamma,
                                                          const float* __restrict__ beta, const float* __restrict__ rmean,
                                                          const float* __restrict__ rvar, float eps, float* __restrict__ Wout,
                                                          long long ld_out, float* __restrict__ bias_out, float* __restrict__ rstd_out,
                                                          long long N, long long K) {
     const long long tid = (long long)blockIdx.x * kBlock + threadIdx.x, stride = (long long)gridDim.x * kBlock;
-    // one rounding per result: the scale gamma * rstd_run stays in fp64 until the product is formed
-    if (Wout) {
-        for (long long i = tid; i < N * K; i += stride) {
-            const long long n = i / K, k = i - n * K;
-            const double sc = (double)gamma[n] / sqrt((double)rvar[n] + (double)eps);
-            Wout[n * ld_out + k] = (float)(sc * (double)W[n * ldw + k]);
-        }
-    }
+    if (Wout) fold_weight(W, ldw, gamma, rvar, eps, Wout, ld_out, N, K, tid, stride);
     for (long long n = tid; n < N; n += stride) {
         const double rs = 1.0 / sqrt((double)rvar[n] + (double)eps);
         if (bias_out) bias_out[n] = (float)((double)beta[n] - (double)rmean[n] * ((double)gamma[n] * rs));
+        if (rstd_out) rstd_out[n] = (float)rs;
+    }
+}
+
+// the layer in front of the BatchNorm has a bias of its own: it is shifted by the running mean before the scale (the difference of two
+// fp32 values is formed in fp64, where it is exact unless their exponents lie more than 29 binades apart)
+__global__ __launch_bounds__(kBlock) void bn_fold_bias_kernel(const float* __restrict__ W, long long ldw,
+                                                              const float* __restrict__ layer_bias, const float* __restrict__ gamma,
+                                                              const float* __restrict__ beta, const float* __restrict__ rmean,
+                                                              const float* __restrict__ rvar, float eps, float* __restrict__ Wout,
+                                                              long long ld_out, float* __restrict__ bias_out,
+                                                              float* __restrict__ rstd_out, long long N, long long K) {
+    const long long tid = (long long)blockIdx.x * kBlock + threadIdx.x, stride = (long long)gridDim.x * kBlock;
+    if (Wout) fold_weight(W, ldw, gamma, rvar, eps, Wout, ld_out, N, K, tid, stride);
+    for (long long n = tid; n < N; n += stride) {
+        const double rs = 1.0 / sqrt((double)rvar[n] + (double)eps);
+        if (bias_out) bias_out[n] = (float)((double)beta[n] + ((double)layer_bias[n] - (double)rmean[n]) * ((double)gamma[n] * rs));
         if (rstd_out) rstd_out[n] = (float)rs;
     }
 }
@@ -625,9 +649,12 @@ extern "C" int dhaug_bn_act_backward(const void* z, int z_bf16, int64_t ld_z, co
     return dhaug_launch_status();
 }
 
-extern "C" int dhaug_bn_fold(const float* W, int64_t ldw, const float* gamma, const float* beta, const float* running_mean,
-                             const float* running_var, float eps, float* W_out, int64_t ld_out, float* bias_out, float* rstd_out,
-                             int64_t N, int64_t K, void* stream) {
+namespace {
+
+// the two fold entry points: layer_bias == nullptr launches dhaug_bn_fold's own kernel
+int fold_launch(const float* W, int64_t ldw, const float* layer_bias, const float* gamma, const float* beta,
+                const float* running_mean, const float* running_var, float eps, float* W_out, int64_t ld_out, float* bias_out,
+                float* rstd_out, int64_t N, int64_t K, void* stream) {
     DHAUG_CHECK(N >= 0 && K >= 0 && eps >= 0.0f, DHAUG_EINVAL);
     if (N == 0) return DHAUG_OK;
     DHAUG_CHECK_PTR(gamma); DHAUG_CHECK_PTR(beta); DHAUG_CHECK_PTR(running_mean); DHAUG_CHECK_PTR(running_var);
@@ -636,10 +663,31 @@ extern "C" int dhaug_bn_fold(const float* W, int64_t ldw, const float* gamma, co
     DHAUG_CHECK(N < kMaxCols && K < kMaxCols, DHAUG_EUNSUPPORTED);
     DHAUG_CHECK(W_out == nullptr || (ldw >= K && ld_out >= K), DHAUG_EALIGN);
     DHAUG_CHECK(aligned(W, 4) && aligned(W_out, 4) && aligned(gamma, 4) && aligned(beta, 4) && aligned(running_mean, 4) &&
-                aligned(running_var, 4) && aligned(bias_out, 4) && aligned(rstd_out, 4), DHAUG_EALIGN);
+                aligned(running_var, 4) && aligned(bias_out, 4) && aligned(rstd_out, 4) && aligned(layer_bias, 4), DHAUG_EALIGN);
     const int64_t items = W_out ? (N * K > N ? N * K : N) : N;
-    hipLaunchKernelGGL(bn_fold_kernel, dim3(dhaug_stream_grid(items, kBlock)), dim3(kBlock), 0, (hipStream_t)stream, W,
-                       (long long)ldw, gamma, beta, running_mean, running_var, eps, K == 0 ? nullptr : W_out, (long long)ld_out,
-                       bias_out, rstd_out, (long long)N, (long long)K);
+    const dim3 grid(dhaug_stream_grid(items, kBlock));
+    if (layer_bias)
+        hipLaunchKernelGGL(bn_fold_bias_kernel, grid, dim3(kBlock), 0, (hipStream_t)stream, W, (long long)ldw, layer_bias, gamma, beta,
+                           running_mean, running_var, eps, K == 0 ? nullptr : W_out, (long long)ld_out, bias_out, rstd_out,
+                           (long long)N, (long long)K);
+    else
+        hipLaunchKernelGGL(bn_fold_kernel, grid, dim3(kBlock), 0, (hipStream_t)stream, W, (long long)ldw, gamma, beta, running_mean,
+                           running_var, eps, K == 0 ? nullptr : W_out, (long long)ld_out, bias_out, rstd_out, (long long)N,
+                           (long long)K);
     return dhaug_launch_status();
+}
+
+}  // namespace
+
+extern "C" int dhaug_bn_fold(const float* W, int64_t ldw, const float* gamma, const float* beta, const float* running_mean,
+                             const float* running_var, float eps, float* W_out, int64_t ld_out, float* bias_out, float* rstd_out,
+                             int64_t N, int64_t K, void* stream) {
+    return fold_launch(W, ldw, nullptr, gamma, beta, running_mean, running_var, eps, W_out, ld_out, bias_out, rstd_out, N, K, stream);
+}
+
+extern "C" int dhaug_bn_fold_bias(const float* W, int64_t ldw, const float* layer_bias, const float* gamma, const float* beta,
+                                  const float* running_mean, const float* running_var, float eps, float* W_out, int64_t ld_out,
+                                  float* bias_out, float* rstd_out, int64_t N, int64_t K, void* stream) {
+    return fold_launch(W, ldw, layer_bias, gamma, beta, running_mean, running_var, eps, W_out, ld_out, bias_out, rstd_out, N, K,
+                       stream);
 }

@@ -1,7 +1,7 @@
 """Drop-in for R/function_baseline/model_pos_preparation.py (model_pos_preparation :18-87): builds the posenet the augmentation
-trains.  Of the reference's five posenet names this package implements three, each through a factory of its own: `videopose` (the
-default run's single-frame model, model_pos_preparation), `mulit_farme_videopose` (multi_frame_model_pos_preparation) and `gcn`
-(gcn_model_pos_preparation).  `mlp` and `mulit_farme_poseformer` are not implemented."""
+trains.  Of the reference's five posenet names this package implements four, each through a factory of its own: `videopose` (the
+default run's single-frame model, model_pos_preparation), `mulit_farme_videopose` (multi_frame_model_pos_preparation), `gcn`
+(gcn_model_pos_preparation) and `mlp` (mlp_model_pos_preparation).  `mulit_farme_poseformer` is not implemented."""
 import torch
 
 from ..models_baseline.videopose.model_VideoPose3D import TemporalModelOptimized1f
@@ -13,8 +13,8 @@ REFERENCE_POSENETS = ("gcn", "mlp", "videopose", "mulit_farme_videopose", "mulit
 def _finish(args, name, model_pos, device, described):
     """the factories' common tail: the line that describes the model (`described` with the parameter count and the precision put
     behind it), then, with args.pretrain, ckpt['model_pos'] of args.posenet_pretrain_path; otherwise the constructors'
-    initialisation stays (the reference applies its init_weights here, which touches nn.Linear modules only, and these models hold
-    none)"""
+    initialisation stays (the reference applies its init_weights here, which touches nn.Linear modules only: of these models only
+    the MLP holds any, and its factory has applied it by then)"""
     count = sum(p.numel() for p in model_pos.parameters())
     print("posenet %s, %d parameters (%.2f M), precision %s" % (described, count, count / 1e6, model_pos.precision))
     if getattr(args, "pretrain", False):
@@ -76,4 +76,25 @@ def gcn_model_pos_preparation(args, dataset, device, flag='train'):
     skeleton = getattr(dataset, "skeleton", None)
     adj = adj_mx_from_skeleton(skeleton()) if callable(skeleton) else adj_mx_from_parents(H36M_PARENTS)
     model_pos = SemGCN(adj, 128, num_layers=int(args.stages), p_dropout=args.dropout, nodes_group=None).to(device)
+    return _finish(args, name, model_pos, device, "%s: %d stages" % (name, int(args.stages)))
+
+
+MLP_POSENETS = ("mlp",)
+
+
+def mlp_model_pos_preparation(args, dataset, device, flag='train'):
+    """the reference's `mlp` branch (R/function_baseline/model_pos_preparation.py:31-32): the MLP posenet (B, 16, 2) -> (B, 16, 3),
+    LinearModel(32, 45, num_stage=args.stages, p_dropout=args.dropout).  Without args.pretrain the weights are init_weights'
+    (kaiming_normal_), drawn on the HOST generator before the move to `device`: on a CPU device one seed gives the reference's
+    weights; on a GPU device the reference draws them from the device generator (it moves the model first), so the same seed gives
+    other weights there.  A factory of its own: model_pos_preparation above keeps refusing every name but `videopose`."""
+    from ..models_baseline.mlp import LinearModel, init_weights
+    name = args.posenet_name
+    if name not in MLP_POSENETS:
+        raise NotImplementedError("posenet_name %r is not an MLP posenet of this package; implemented: %s"
+                                  % (name, ", ".join(MLP_POSENETS)))
+    model_pos = LinearModel(32, 45, num_stage=int(args.stages), p_dropout=args.dropout)
+    if not getattr(args, "pretrain", False):
+        model_pos.apply(init_weights)
+    model_pos = model_pos.to(device)
     return _finish(args, name, model_pos, device, "%s: %d stages" % (name, int(args.stages)))

@@ -22,7 +22,11 @@ in both directions, between the classes too, and one seed gives the reference's 
               given.  The folded and packed operands are cached on the module until a weight, a BatchNorm parameter or a running
               buffer changes.
 Everything else is a few lines of plain torch: CPU tensors, evaluation mode with gradients on, and the dilated class in training
-mode (the reference never trains it).  Causal and dense convolutions are not implemented (the reference's drivers set neither)."""
+mode (the reference never trains it).  Causal and dense convolutions are not implemented (the reference's drivers set neither).
+
+The row-layer paths also serve models_baseline/mlp/linear_model.py (LinearModel derives from TemporalModelOptimized1f): a layer may
+be an nn.Linear (a 2-D weight) and may have a bias in front of its BatchNorm -- see _bias_before_bn for training, and in evaluation
+the fold carries it through the BatchNorm (dhaug_bn_fold_bias).  The VideoPose layers have no bias and take the calls they took."""
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
@@ -80,8 +84,7 @@ class multiFrame_TemporalModelBase(nn.Module):
 
     # ------------------------------------------------------------------------------------------------ the reference's interface
     def set_bn_momentum(self, momentum):
-        self.expand_bn.momentum = momentum
-        for bn in self.layers_bn:
+        for _, bn, _, _, _ in self._layers():
             bn.momentum = momentum
 
     def receptive_field(self):
@@ -109,7 +112,8 @@ class multiFrame_TemporalModelBase(nn.Module):
         return A.ORDERED6 if prec == "bf16x6" else prec
 
     def _layers(self):
-        """(conv, bn, adds the block's input, taps, dilation) of every hidden layer"""
+        """(conv, bn, adds the block's input, taps, dilation) of every hidden layer.  What the paths below read of a layer: .weight
+        ((N, Cin, k), or (N, Cin) of an nn.Linear) and .bias (None in the VideoPose networks; see _bias_before_bn)"""
         out = [(self.expand_conv, self.expand_bn, False, self.filter_widths[0], 1)]
         dilation = self.filter_widths[0]
         for i, w in enumerate(self.filter_widths[1:]):
@@ -117,6 +121,22 @@ class multiFrame_TemporalModelBase(nn.Module):
             out.append((self.layers_conv[2 * i + 1], self.layers_bn[2 * i + 1], True, 1, 1))
             dilation *= w
         return out
+
+    def _head(self):
+        """the output layer, Conv(1) / Linear + bias"""
+        return self.shrink
+
+    def _p(self):
+        """the dropout rate behind every hidden layer"""
+        return float(self.drop.p)
+
+    def _bias_before_bn(self, layer):
+        """the bias of a layer whose output goes into a BatchNorm (the nn.Linear layers of models_baseline/mlp), as the layer's GEMM
+        adds it.  Under batch statistics it is a constant: BatchNorm subtracts the batch mean, so its gradient is zero in exact
+        arithmetic and rounding residue otherwise -- it is added detached (running_mean comes out right by itself, no column sum is
+        launched for it, and no optimizer moves it).  Under the running statistics its gradient is real and it stays attached."""
+        b = layer.bias
+        return b if b is None or not self.training else b.detach()
 
     def forward(self, x):
         name = type(self).__name__
@@ -175,7 +195,10 @@ class multiFrame_TemporalModelBase(nn.Module):
     # ------------------------------------------------------------------------------------------------ training (strided class)
     @staticmethod
     def _w2d(conv):
-        """the (N, K) matrix of a width-1 convolution; its packed copies are cached on the parameter (autograd_ops._pack)"""
+        """the (N, K) matrix of a width-1 convolution (an nn.Linear's weight is one as it is); its packed copies are cached on the
+        parameter (autograd_ops._pack)"""
+        if conv.weight.dim() == 2:
+            return conv.weight
         W = conv.weight.view(conv.weight.shape[0], conv.weight.shape[1])
         W._dhaug_owner = conv.weight
         return W
@@ -183,29 +206,32 @@ class multiFrame_TemporalModelBase(nn.Module):
     def _forward_train(self, h):
         prec = self._layer_precision()
         f32 = prec != "bf16"
-        C, p = self.channels, float(self.drop.p)
+        C, p = self.channels, self._p()
         res = None
-        for conv, bn, residual, k, _ in self._layers():
+        layers, head = self._layers(), self._head()
+        for conv, bn, residual, k, _ in layers:
             if bn.momentum is None:
                 raise NotImplementedError("%s: cumulative moving average (momentum=None) is not implemented" % type(self).__name__)
-            if not residual and conv is not self.expand_conv:
+            if not residual and conv is not layers[0][0]:
                 # what the block's second layer adds: rows k r + k // 2 of the block input, read where they lie (k = 1: the block
                 # input itself, not a view of it -- no node in the graph, and bf16 rows padded beyond C stay what they are)
                 res = h if k == 1 else h.view(h.shape[0] // k, k, C)[:, k // 2]
             if k == 1:
-                z = A.linear(h, self._w2d(conv), None, None, A.ACT_NONE, 0.0, prec, out_f32=f32)
+                z = A.linear(h, self._w2d(conv), self._bias_before_bn(conv), None, A.ACT_NONE, 0.0, prec, out_f32=f32)
             else:
                 z = A.conv_taps(h, conv.weight, k, prec, out_f32=f32)
             h = A.bn_act(z, bn.weight, bn.bias, res if residual else None,
                          (bn.running_mean, bn.running_var, bn.num_batches_tracked), bn.momentum, bn.eps, p)
         self._stat_epoch += 1
-        return A.linear(h, self._w2d(self.shrink), self.shrink.bias, None, A.ACT_NONE, 0.0, prec, out_f32=True)
+        return A.linear(h, self._w2d(head), head.bias, None, A.ACT_NONE, 0.0, prec, out_f32=True)
 
     # ------------------------------------------------------------------------------------------------ evaluation (both classes)
     def _eval_key(self):
-        key = [self._arithmetic(), self._stat_epoch, A.pack_key(self.shrink.weight), A.tensor_state(self.shrink.bias)]
+        head = self._head()
+        key = [self._arithmetic(), self._stat_epoch, A.pack_key(head.weight), A.tensor_state(head.bias)]
         for conv, bn, _, _, _ in self._layers():
             key += [A.pack_key(conv.weight)] + [A.tensor_state(t) for t in (bn.weight, bn.bias, bn.running_mean, bn.running_var)] + [bn.eps]
+            key.append(None if conv.bias is None else A.tensor_state(conv.bias))      # (folded into the operands like the rest)
         return key
 
     def _operand(self, W, Cin, k):
@@ -224,9 +250,11 @@ class multiFrame_TemporalModelBase(nn.Module):
             for conv, bn, residual, k, _ in self._layers():
                 W = conv.weight.detach().flatten(1)
                 Wf, bias, rstd = ops.bn_fold(W, bn.weight.detach(), bn.bias.detach(), bn.running_mean, bn.running_var, bn.eps,
-                                             want_weight=not residual)
-                layers.append((self._operand(W if residual else Wf, conv.weight.shape[1], k), None if residual else bias, rstd))
-            self._eval_cache = (key, layers, self._operand(self.shrink.weight.detach().flatten(1), self.channels, 1))
+                                             want_weight=not residual, layer_bias=conv.bias)
+                if residual:                    # (the GEMM stays the layer's own, bias included: BatchNorm runs behind it)
+                    bias = None if conv.bias is None else conv.bias.detach()
+                layers.append((self._operand(W if residual else Wf, conv.weight.shape[1], k), bias, rstd))
+            self._eval_cache = (key, layers, self._operand(self._head().weight.detach().flatten(1), self.channels, 1))
         return self._eval_cache[1], self._eval_cache[2]
 
     def _gemm(self, a, B, N, K, bias, act, out_f32=False):
@@ -241,18 +269,18 @@ class multiFrame_TemporalModelBase(nn.Module):
 
     def _forward_eval(self, h, nseq, t_in):
         layers, shrink = self._folded()
-        C = self.channels
+        C, head, first = self.channels, self._head(), self._layers()[0][0]
         bf16 = self._arithmetic() == "bf16"
         res = None
         for (conv, bn, residual, k, dilation), (Bop, bias, rstd) in zip(self._layers(), layers):
             N, Cin = conv.weight.shape[0], conv.weight.shape[1]
             if residual:
-                z = self._gemm(h, Bop, N, Cin, None, A.ACT_NONE)
+                z = self._gemm(h, Bop, N, Cin, bias, A.ACT_NONE)
                 yb, yf, _, _ = ops.bn_act_forward(z, N, bn.weight.detach(), bn.bias.detach(), residual=res,
                                                   stats=(bn.running_mean, rstd))
                 h = yb if yb is not None else yf
                 continue
-            block = conv is not self.expand_conv
+            block = conv is not first
             if k == 1:                                  # (in either class: h itself, whose bf16 rows may be padded beyond C)
                 a = res = h
             elif self.STRIDED:
@@ -268,7 +296,7 @@ class multiFrame_TemporalModelBase(nn.Module):
                 a = ab if bf16 else af
                 t_in -= 2 * pad
             h = self._gemm(a, Bop, N, k * Cin, bias, A.ACT_RELU)
-        return self._gemm(h, shrink, self.shrink.weight.shape[0], C, self.shrink.bias.detach(), A.ACT_NONE, out_f32=True)
+        return self._gemm(h, shrink, head.weight.shape[0], C, head.bias.detach(), A.ACT_NONE, out_f32=True)
 
 
 class TemporalModelOptimized1f(multiFrame_TemporalModelBase):
@@ -294,8 +322,8 @@ class TemporalModelOptimized1f(multiFrame_TemporalModelBase):
         B = x.shape[0]
         width = self.num_joints_in * self.in_features
         if x.dim() not in (2, 3) or x.numel() != B * width:
-            raise ValueError("TemporalModelOptimized1f: input must be (B, %d, %d) or (B, %d), got %s"
-                             % (self.num_joints_in, self.in_features, width, tuple(x.shape)))
+            raise ValueError("%s: input must be (B, %d, %d) or (B, %d), got %s"
+                             % (type(self).__name__, self.num_joints_in, self.in_features, width, tuple(x.shape)))
         y = self._run(x.reshape(B, 1, width), (B, self.channels))
         return F.pad(y, (3, 0)).view(B, self.num_joints_out + 1, 3)          # the hip joint: zeros in front
 
@@ -305,12 +333,13 @@ class TemporalModelOptimized1f(multiFrame_TemporalModelBase):
         for conv, bn, residual, _, _ in self._layers():
             if not residual:
                 block_in = h
-            z = F.linear(h, conv.weight.flatten(1))
+            z = F.linear(h, conv.weight.flatten(1), self._bias_before_bn(conv))
             z = F.batch_norm(z, bn.running_mean, bn.running_var, bn.weight, bn.bias, self.training, bn.momentum, bn.eps)
             if self.training:
                 with torch.no_grad():
                     bn.num_batches_tracked.add_(1)
-            h = F.dropout(F.relu(z), self.drop.p, self.training)
+            h = F.dropout(F.relu(z), self._p(), self.training)
             if residual:
                 h = block_in + h
-        return F.linear(h, self.shrink.weight.flatten(1), self.shrink.bias)
+        head = self._head()
+        return F.linear(h, head.weight.flatten(1), head.bias)

@@ -1258,8 +1258,9 @@ def bn_act_backward(z, C, g, gamma, beta, mean, rstd, p=0.0, rng=(0, 0), workspa
     return dzb, dzf, dgamma, dbeta
 
 
-def bn_fold(W, gamma, beta, running_mean, running_var, eps=1e-5, want_weight=True):
-    """evaluation-mode BatchNorm folded into the (N, K) layer in front of it (dhaug_bn_fold): returns (W' | None, b', rstd_run)"""
+def bn_fold(W, gamma, beta, running_mean, running_var, eps=1e-5, want_weight=True, layer_bias=None):
+    """evaluation-mode BatchNorm folded into the (N, K) layer in front of it (dhaug_bn_fold): returns (W' | None, b', rstd_run).
+    layer_bias: the layer's own bias (N fp32), which b' then carries through the BatchNorm (dhaug_bn_fold_bias)"""
     N = gamma.numel()
     v = [_bn_vec(t, N, "bn_fold", n) for t, n in ((gamma, "gamma"), (beta, "beta"), (running_mean, "running_mean"),
                                                   (running_var, "running_var"))]
@@ -1271,8 +1272,13 @@ def bn_fold(W, gamma, beta, running_mean, running_var, eps=1e-5, want_weight=Tru
         K = Wd.shape[1]
         Wo = torch.empty_like(Wd)
     bias, rstd = torch.empty(N, dtype=torch.float32, device=dev), torch.empty(N, dtype=torch.float32, device=dev)
-    _lib.call("dhaug_bn_fold", _p(Wd), K, _p(v[0]), _p(v[1]), _p(v[2]), _p(v[3]), float(eps), _p(Wo), K, _p(bias), _p(rstd), N, K,
-              _stream())
+    if layer_bias is None:
+        _lib.call("dhaug_bn_fold", _p(Wd), K, _p(v[0]), _p(v[1]), _p(v[2]), _p(v[3]), float(eps), _p(Wo), K, _p(bias), _p(rstd), N, K,
+                  _stream())
+    else:
+        lb = _bn_vec(layer_bias.detach(), N, "bn_fold", "layer_bias")
+        _lib.call("dhaug_bn_fold_bias", _p(Wd), K, _p(lb), _p(v[0]), _p(v[1]), _p(v[2]), _p(v[3]), float(eps), _p(Wo), K, _p(bias),
+                  _p(rstd), N, K, _stream())
     return Wo, bias, rstd
 
 

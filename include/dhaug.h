@@ -919,6 +919,11 @@ int dhaug_add_f32(const float* a, const float* b, float* out, int64_t n, void* s
  * dhaug_bn_fold (evaluation): W_out[n, :] = gamma[n] * rstd_run[n] * W[n, :] (N, K) fp32, bias_out[n] = beta[n] - running_mean[n] *
  *   gamma[n] * rstd_run[n], rstd_out[n] = rstd_run[n] = 1 / sqrt(running_var[n] + eps); each output optional (at least one), each
  *   value formed in fp64 and rounded once.
+ * dhaug_bn_fold_bias: dhaug_bn_fold for a layer that has a bias of its own in front of the BatchNorm (the nn.Linear layers of
+ *   R/models_baseline/mlp/linear_model.py), layer_bias (N fp32, optional) behind W, ldw.  W_out and rstd_out as dhaug_bn_fold;
+ *     bias_out[n] = beta[n] + (layer_bias[n] - running_mean[n]) * gamma[n] * rstd_run[n],
+ *   formed in fp64 and rounded once.  layer_bias = NULL is a zero bias: dhaug_bn_fold's own launch, every output bit-identical to
+ *   its.  The same codes and alignment rules (layer_bias 4-byte aligned); N = 0 is a no-op that looks at no pointer.
  * All: DHAUG_EINVAL for M, C, N, K < 0, a z_bf16 outside {0, 1}, p outside [0, 1), a NULL required pointer, no output; an empty
  * batch (M = 0 or C = 0; N = 0) is a no-op that looks at no pointer. */
 #define DHAUG_BN_MAX_CHUNKS 32
@@ -938,6 +943,9 @@ int dhaug_bn_act_backward(const void* z, int z_bf16, int64_t ld_z, const void* g
 int dhaug_bn_fold(const float* W, int64_t ldw, const float* gamma, const float* beta, const float* running_mean,
                   const float* running_var, float eps, float* W_out, int64_t ld_out, float* bias_out, float* rstd_out, int64_t N,
                   int64_t K, void* stream);
+int dhaug_bn_fold_bias(const float* W, int64_t ldw, const float* layer_bias, const float* gamma, const float* beta,
+                       const float* running_mean, const float* running_var, float eps, float* W_out, int64_t ld_out,
+                       float* bias_out, float* rstd_out, int64_t N, int64_t K, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------
  * Multi-frame VideoPose posenets: the tap layout around the GEMMs (R/models_Fk_GAN/mulit_farme_videopose.py; csrc/dhaug_taps.hip)
