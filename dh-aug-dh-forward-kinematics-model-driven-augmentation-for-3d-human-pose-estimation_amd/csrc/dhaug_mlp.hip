@@ -23,6 +23,7 @@
 //     workgroup-uniform.
 #include <cstdlib>
 #include "dhaug_common.h"
+#include "dhaug_out_copy.h"
 
 namespace {
 
@@ -63,7 +64,7 @@ struct Unit {
     int src2, ksteps2;          // optional second source (layers fed by a concatenation), ksteps2 = 0: none
     int ksteps, N, act;
     float slope;
-    int cols;                   // LOAD / STORE: columns moved
+    int cols;                   // LOAD / STORE: columns moved.  fp32 output layer with PLAN_VSTORE: outc_magic(N) (dhaug_out_copy.h)
     long long ld;               // leading dimension (elements) of the global tensor
     const void* g;              // LOAD source / STORE destination / fp32 output of the last layer
     const uint16_t* w;          // GEMM: packed fragments [slice][kstep][64 lanes][8]
@@ -83,6 +84,9 @@ enum { PLAN_STACK = 1 << 13, PLAN_LEAKY = 1 << 10, PLAN_ALT = 1 << 11, PLAN_TAIL
 // lead layer it feeds run as ONE dispatch and the lead takes its operand from global memory (stack_lead_global); the rest of the
 // word is then that stack's plan with the lead's true k-steps (cols / 16: 2 or 3) in bits 0-3
 enum { PLAN_LEADG = 1 << 15 };
+// plan of an fp32 output layer (F_OUT_F32; a single-layer word, also where the layer runs as a stack's tail): its rows are
+// contiguous in memory and the launch is an inference launch -- the tile leaves as 16-byte groups (store_output_linear)
+enum { PLAN_VSTORE = 1 << 8 };
 
 struct Program {
     int nunits;
@@ -125,7 +129,10 @@ typedef const Unit __attribute__((address_space(4))) * UnitPtr;      // units ar
 #define DHAUG_STAMP_TID 0
 #endif
 // development aid (not built by default): shader-clock stamps of workgroup 0 at every unit boundary of its first tile
-__device__ long long g_mlp_stamps[5 * MLP_MAX_UNITS + 68 + MLP_MAX_UNITS + 1];
+// (+ 4 per unit behind those: start and end of the unit's copy-out -- store_output / dot_output -- first tile, later tile)
+__device__ long long g_mlp_stamps[5 * MLP_MAX_UNITS + 68 + MLP_MAX_UNITS + 1 + 4 * MLP_MAX_UNITS];
+#define DHAUG_OSTAMP(unit, k)     \
+    if (blockIdx.x == 0 && tid == 0) g_mlp_stamps[6 * MLP_MAX_UNITS + 69 + (tile == 0 ? 0 : 2 * MLP_MAX_UNITS) + 2 * (unit) + (k)] = (long long)__builtin_readcyclecounter();
 #define DHAUG_STAMP(idx)                                                      \
     if (blockIdx.x == 0 && tid == 0) g_mlp_stamps[tile == 0 ? (idx) : 5 * MLP_MAX_UNITS + 68 + (idx)] = (long long)__builtin_readcyclecounter();
 #ifdef DHAUG_MLP_TIMING_UNITS                                 /* unit boundaries only: the layer bodies compile as shipped */
@@ -137,6 +144,7 @@ __device__ long long g_mlp_stamps[5 * MLP_MAX_UNITS + 68 + MLP_MAX_UNITS + 1];
 #else
 #define DHAUG_STAMP(idx)
 #define DHAUG_LSTAMP(idx)
+#define DHAUG_OSTAMP(unit, k)
 #endif
 // ends the basic block (a never-taken scalar branch the compiler cannot see through): the 32-row tiles of a stack layer
 // are scheduled and register-allocated one at a time instead of as one 1 200-instruction block
@@ -1412,12 +1420,63 @@ __device__ __forceinline__ void dot_output(UnitPtr u, unsigned char* smem, long 
     static_cast<float*>(const_cast<void*>(u->g))[(m0 + tid) * u->ld] = s;
 }
 
-__device__ __forceinline__ void store_output(UnitPtr u, unsigned char* smem, long long m0, long long M, int tid) {
-    const float* st = reinterpret_cast<const float*>(buf_base(smem, u->dst));
-    float* out = static_cast<float*>(const_cast<void*>(u->g));
-    const long long ld = u->ld;
-    for (Sweep sw(tid, u->N); sw.row < MLP_BM; sw.next())
+// The same with every request in front of the first add (inference launches): the rolled loop above is eight dependent
+// ds_read -> wait -> add trips between two barriers.  Same order of additions, starting from +0; the partial sums of waves that
+// own no slice are neither read nor added (that LDS may hold anything).
+__device__ __forceinline__ void dot_output_once(UnitPtr u, unsigned char* smem, long long m0, long long M, int tid) {
+    asm volatile("" : "+v"(tid));
+    if (tid >= MLP_BM || m0 + tid >= M) return;
+    const float* st = reinterpret_cast<const float*>(buf_base(smem, u->dst)) + tid;
+    const int nw = min(4, (u->N + 31) >> 5);
+    float p[8];
+#pragma unroll
+    for (int w = 0; w < 4; ++w)
+        if (w < nw) { p[2 * w] = st[2 * w * MLP_BM]; p[2 * w + 1] = st[(2 * w + 1) * MLP_BM]; }
+    float s = 0.f;
+#pragma unroll
+    for (int w = 0; w < 4; ++w)
+        if (w < nw) { s += p[2 * w]; s += p[2 * w + 1]; }
+    static_cast<float*>(const_cast<void*>(u->g))[(m0 + tid) * u->ld] = s;
+}
+
+__device__ __forceinline__ void store_output(const float* st, float* out, long long ld, int N, long long m0, long long M, int tid) {
+    for (Sweep sw(tid, N); sw.row < MLP_BM; sw.next())
         if (m0 + sw.row < M) out[(m0 + sw.row) * ld + sw.c] = st[sw.row * OUT_PITCH + sw.c];
+}
+__device__ __forceinline__ void store_output(UnitPtr u, unsigned char* smem, long long m0, long long M, int tid) {
+    store_output(reinterpret_cast<const float*>(buf_base(smem, u->dst)), static_cast<float*>(const_cast<void*>(u->g)), u->ld, u->N, m0, M, tid);
+}
+
+// the copy-out of an fp32 output unit / of a DOT_OUT layer's logits as the plan routes them; the forward-with-save instantiation
+// keeps the loops (its code is what it was)
+template <bool SAVE>
+__device__ __forceinline__ void output_unit(UnitPtr u, unsigned char* smem, long long m0, long long M, int tid) {
+    if constexpr (SAVE) {
+        store_output(u, smem, m0, M, tid);
+    } else {
+#ifdef OUT_ABL_ROLLED                                         /* stamp builds: the rolled loops in the inference unit too */
+        if (true) { store_output(u, smem, m0, M, tid); return; }
+#endif
+        // everything the unit says in ONE batch of scalar loads, in front of the branch (the plan word on its own would be a second
+        // round trip to the constant cache).  PLAN_VSTORE: the rows are contiguous (ld == N), the tile is one linear array
+        // (dhaug_out_copy.h); cols then holds the row magic of N (mlp_prepare).
+        static_assert(OUT_PITCH == OUTC_PITCH && MLP_BM == OUTC_BM, "staging image");
+        asm volatile("" : "+v"(tid));                                        // opaque: nothing derived from it is hoisted out of the tile loop
+        const int plan = u->plan, N = u->N, magic = u->cols;
+        const long long ld = u->ld;
+        const float* st = reinterpret_cast<const float*>(buf_base(smem, u->dst));
+        float* out = static_cast<float*>(const_cast<void*>(u->g));
+        if (plan & PLAN_VSTORE) outc_copy_linear<MLP_THREADS>(st, out, N, (uint32_t)magic, m0, M, tid);
+        else store_output(st, out, ld, N, m0, M, tid);
+    }
+}
+template <bool SAVE>
+__device__ __forceinline__ void logit_unit(UnitPtr u, unsigned char* smem, long long m0, long long M, int tid) {
+#ifdef OUT_ABL_ROLLED
+    if (true) { dot_output(u, smem, m0, M, tid); return; }
+#endif
+    if constexpr (SAVE) dot_output(u, smem, m0, M, tid);
+    else dot_output_once(u, smem, m0, M, tid);
 }
 
 template <bool SAVE>
@@ -1484,8 +1543,10 @@ __global__ __launch_bounds__(MLP_THREADS, 1) void fused_mlp_kernel(Program prog,
                             save_image(tu->dst, tu->save, tu->save_ld, (tu->N + 15) & ~15, smem, m0, tu->save_rows, tid);
                     }
                     if (tail == 1) {
-                        store_output(tu, smem, m0, M, tid);
+                        DHAUG_OSTAMP(ui, 0)
+                        output_unit<SAVE>(tu, smem, m0, M, tid);
                         lds_barrier();                       // (not __syncthreads: nobody waits for the stores to be acknowledged)
+                        DHAUG_OSTAMP(ui, 1)
                     }
 
                     continue;                                                // (stamps of the run's inner layers stay 0)
@@ -1495,9 +1556,11 @@ __global__ __launch_bounds__(MLP_THREADS, 1) void fused_mlp_kernel(Program prog,
                     gemm_pair(u, u + 1, smem, wave, lane, dbg);
                     if ((u + 1)->flags & F_DOT_OUT) {
                         lds_barrier();
-                        dot_output(u + 1, smem, m0, M, tid);
+                        DHAUG_OSTAMP(ui, 0)
+                        logit_unit<SAVE>(u + 1, smem, m0, M, tid);
                     }
                     lds_barrier();
+                    DHAUG_OSTAMP(ui, 1)
                     DHAUG_LSTAMP(dbg + 7)
                     continue;
                 }
@@ -1516,14 +1579,17 @@ __global__ __launch_bounds__(MLP_THREADS, 1) void fused_mlp_kernel(Program prog,
 #undef DHAUG_SHAPES
                 if (plan & PLAN_OUT) {
                     lds_barrier();
-                    store_output(u, smem, m0, M, tid);
+                    DHAUG_OSTAMP(ui, 0)
+                    output_unit<SAVE>(u, smem, m0, M, tid);
                 }
                 if (plan & PLAN_DOT) {
                     lds_barrier();
-                    dot_output(u, smem, m0, M, tid);
+                    DHAUG_OSTAMP(ui, 0)
+                    logit_unit<SAVE>(u, smem, m0, M, tid);
                 }
             }
             lds_barrier();
+            if (kind == U_GEMM && (plan & (PLAN_OUT | PLAN_DOT))) { DHAUG_OSTAMP(ui, 1) }
             if (SAVE && kind == U_GEMM && !(plan & (PLAN_OUT | PLAN_DOT)) && u->save != nullptr)
                 save_image(u->dst, u->save, u->save_ld, (u->N + 15) & ~15, smem, m0, u->save_rows, tid);
             DHAUG_LSTAMP(MLP_MAX_UNITS + 64 + 4 * ui + 3)
@@ -1618,11 +1684,15 @@ __global__ __launch_bounds__(256) void pack_wfrag_desc_kernel(const dhaug_wfrag_
 
 // how unit i is executed (see the dispatch in fused_mlp_kernel): a run of >= min_run full-width 256 -> 256 layers goes to
 // gemm_stack, together with the narrow layer (K <= 128) feeding it and the <= 64-wide fp32 output layer behind it
-// leadg: may a bf16 LOAD and the stack behind it become one dispatch whose lead layer reads the tensor from global memory
+// infer (an inference launch): may a bf16 LOAD and the stack behind it become one dispatch whose lead layer reads the tensor from global memory
 // (PLAN_LEADG)?  Inference launches only; DHAUG_MLP_NOLEADG in the environment turns the route off (A/B runs, tests).
-int plan_unit(const Program& p, int i, bool leadg = false) {
+// An fp32 output unit whose rows are contiguous (ld == N, 16-byte aligned base) leaves as 16-byte groups (PLAN_VSTORE) in an
+// inference launch; DHAUG_MLP_NOVSTORE in the environment keeps the rolled loop (A/B runs, tests).
+int plan_unit(const Program& p, int i, bool infer = false) {
     const Unit* U = p.u;
     const Unit& u = U[i];
+    const int vstore = (infer && u.kind == U_GEMM && (u.flags & F_OUT_F32) && u.ld == u.N && u.N <= 64 && dhaug_aligned16(u.g) &&
+                        !getenv("DHAUG_MLP_NOVSTORE")) ? PLAN_VSTORE : 0;
     if (u.kind != U_GEMM) {
         // a bf16 LOAD may read back rows a STORE of this program parked in global memory: it then drains the workgroup's
         // stores first (full barrier); programs without a STORE skip that wait for write acknowledgements
@@ -1634,7 +1704,7 @@ int plan_unit(const Program& p, int i, bool leadg = false) {
         // image -- it is not written any more -- before buffer dst is written whole again, by a layer of the run (all 256 columns)
         // or by a LOAD.  A unit's own reads come before its write: an in-place residual of the first run layer is a reader.
         // Programs that park rows keep the LOAD (it needs the full barrier first).
-        if (!leadg || parks || getenv("DHAUG_MLP_NOLEADG") || (u.cols != 32 && u.cols != 48) || u.ld > (1 << 20) || i + 1 >= p.nunits)
+        if (!infer || parks || getenv("DHAUG_MLP_NOLEADG") || (u.cols != 32 && u.cols != 48) || u.ld > (1 << 20) || i + 1 >= p.nunits)
             return parks;
         const Unit& l = U[i + 1];
         if (l.kind != U_GEMM || l.src != u.dst) return parks;
@@ -1674,7 +1744,7 @@ int plan_unit(const Program& p, int i, bool leadg = false) {
         const bool pair = !second && i + 1 < p.nunits && narrow(u) && !(u.flags & F_DOT_OUT) && narrow(U[i + 1]) &&
                           !getenv("DHAUG_MLP_NOPAIR");
         return (((c1 + c2) * 16 + c1) << 16) | (((u.N + 31) >> 5) << 24) | ((u.flags & F_OUT_F32) ? PLAN_OUT : 0) |
-               ((u.flags & F_DOT_OUT) ? PLAN_DOT : 0) | (pair ? PLAN_PAIR : 0);
+               ((u.flags & F_DOT_OUT) ? PLAN_DOT : 0) | (pair ? PLAN_PAIR : 0) | vstore;
     }
     const Unit* tu = U + i0 + run;
     const bool tail = i0 + run < p.nunits && tu->kind == U_GEMM && (tu->flags & F_OUT_F32) && tu->ksteps == 16 &&
@@ -1805,6 +1875,8 @@ static int mlp_prepare(const dhaug_mlp_unit* units, int nunits, int64_t M, Progr
     }
     // (forward-with-save keeps its LOADs: fused_mlp_kernel<true> and its schedule are what they were)
     for (int i = 0; i < prog.nunits; ++i) prog.u[i].plan = plan_unit(prog, i, !any_save);
+    for (int i = 0; i < prog.nunits; ++i)                                    // (cols means nothing else to a GEMM unit)
+        if (prog.u[i].kind == U_GEMM && (prog.u[i].plan & PLAN_VSTORE)) prog.u[i].cols = (int)outc_magic(prog.u[i].N);
     {   // sign bits are written by the layers of a run and by the narrow layer feeding it (not by layer-at-a-time units)
         bool in_run[MLP_MAX_UNITS] = {};
         for (int i = 0; i < prog.nunits;) {
@@ -1856,6 +1928,6 @@ int dhaug_mlp_forward(const dhaug_mlp_unit* units, int nunits, int64_t M, void* 
 
 #ifdef DHAUG_MLP_TIMING
 extern "C" int dhaug_debug_mlp_stamps(long long* out, int n) {
-    return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_mlp_stamps), sizeof(long long) * (n < 6 * MLP_MAX_UNITS + 69 ? n : 6 * MLP_MAX_UNITS + 69));
+    return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_mlp_stamps), sizeof(long long) * (n < 10 * MLP_MAX_UNITS + 69 ? n : 10 * MLP_MAX_UNITS + 69));
 }
 #endif

@@ -696,10 +696,13 @@ int dhaug_mlp_forward(const dhaug_mlp_unit* units, int nunits, int64_t M, void* 
 /* Host only, launches nothing: the validation of dhaug_mlp_forward and its planning pass over the same program; plans_out[i]
  * receives how unit i would be executed (an internal encoding, stable enough for tests: bit 13 = a run of full-width layers,
  * DHAUG_MLP_PLAN_LEADG on a bf16 LOAD = the LOAD and the stack behind it run as one unit whose lead layer reads the tensor
- * from global memory instead of an LDS image).  No pointer of the program is dereferenced.  Returns what dhaug_mlp_forward
+ * from global memory instead of an LDS image; DHAUG_MLP_PLAN_VSTORE on an fp32 output layer (DHAUG_MLP_F_OUT_F32, also where it
+ * runs as a stack's tail) = an inference launch whose output rows are contiguous (ld == n, 16-byte aligned g): the tile leaves
+ * as 16-byte groups, not dword by dword; DHAUG_MLP_NOVSTORE in the environment clears it).  No pointer of the program is dereferenced.  Returns what dhaug_mlp_forward
  * would return in front of its launch. */
 #define DHAUG_MLP_PLAN_STACK  (1 << 13)
 #define DHAUG_MLP_PLAN_LEADG  (1 << 15)
+#define DHAUG_MLP_PLAN_VSTORE (1 << 8)
 int dhaug_mlp_plan(const dhaug_mlp_unit* units, int nunits, int64_t M, int32_t* plans_out);
 
 /* Parity-grade variant of the same programs: every operand is an fp16 pair x = hi + lo (22 mantissa bits), a product is

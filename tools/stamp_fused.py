@@ -15,7 +15,7 @@ D2 = Fk_discriminator.Fk_2D_Discriminator(args, 16).cuda()
 x2 = torch.randn(B, 16, 2, device="cuda") * 0.3
 z = torch.randn(B, 128, device="cuda"); x3 = torch.randn(B, 16, 3, device="cuda") * 0.3
 L = _lib.lib()
-N = 6 * 32 + 69
+N = 10 * 32 + 69
 buf = (ctypes.c_longlong * N)()
 # STAMP_CRITICS=1: only the forward's critics launch (both critics in one program, bf16 inputs as Fk_Generator.sample_for_critics
 # hands them over): a stack whose lead reads its operand from global memory shows as ONE unit under its LOAD's index, the lead's
@@ -48,3 +48,10 @@ with torch.no_grad():
         if us:
             b3 = st[96 + 4 * us[0]]
             print("   units(last tile):", " | ".join("%d: %s" % (u, " ".join(str(st[96 + 4 * u + j] - b3) if st[96 + 4 * u + j] else "-" for j in range(4))) for u in us))
+        # copy-out of a unit's outputs (store_output / dot_output): clocks from the unit's start to the copy's start -- the stack or
+        # layer, its closing barrier included -- and the copy itself up to the barrier behind it; first tile, [later tile]
+        for tag, ob, ub in (("first tile", 261, 0), ("later tile", 261 + 64, 228)):
+            outs = [u for u in range(32) if st[ob + 2 * u] and st[ob + 2 * u + 1]]
+            if outs:
+                print("   copy-out (%s):" % tag, " | ".join("%d: %d + %d" % (u, st[ob + 2 * u] - st[ub + u], st[ob + 2 * u + 1] - st[ob + 2 * u])
+                                                              for u in outs))
