@@ -92,10 +92,29 @@ SIGNATURES = {
     "dhaug_graph_mix": [_vp, _i32, _i64, _vp, _vp, _vp, _i32, _i64, _i64, _i64, _i32, _vp],
     "dhaug_graph_adj_grad": [_vp, _i32, _i64, _vp, _i32, _i64, _vp, _i32, _vp, _vp, _i64, _i64, _vp],
     "dhaug_graph_wcat": [_vp, _vp, _i64, _i64, _i32, _vp],
+    "dhaug_layernorm_forward": [_vp, _i32, _i64, _vp, _vp, _f32, _vp, _i32, _i64, _vp, _vp, _i64, _i64, _vp],
+    "dhaug_layernorm_backward": [_vp, _i32, _i64, _vp, _i32, _i64, _vp, _vp, _vp, _vp, _i32, _i64, _vp, _vp, _vp, _i64, _i64, _vp],
+    "dhaug_attn_forward": [_vp, _i32, _i64, _vp, _i32, _i64, _vp, _i64, _i32, _i32, _i32, _f32, _vp],
+    "dhaug_attn_backward": [_vp, _i32, _i64, _vp, _i32, _i64, _vp, _vp, _i32, _i64, _vp, _i32, _i64, _i64, _i32, _i32, _i32, _f32, _vp],
+    "dhaug_gelu_forward": [_vp, _i64, _vp, _i32, _i64, _i64, _i64, _vp],
+    "dhaug_gelu_backward": [_vp, _i64, _vp, _i32, _i64, _vp, _i32, _i64, _i64, _i64, _vp],
 }
 BN_MAX_CHUNKS = 32                                     # DHAUG_BN_MAX_CHUNKS of include/dhaug.h
 GRAPH_MAX_PAIRS = 256                                  # DHAUG_GRAPH_MAX_PAIRS
 GRAPH_ADJ_WORKSPACE_DOUBLES = 64 * GRAPH_MAX_PAIRS     # DHAUG_GRAPH_ADJ_WORKSPACE_DOUBLES
+LAYERNORM_MAX_COLS = 2048                              # DHAUG_LAYERNORM_MAX_COLS
+LAYERNORM_MAX_BLOCKS = 256                             # DHAUG_LAYERNORM_MAX_BLOCKS
+LAYERNORM_PARTIAL_ROWS = 8                             # DHAUG_LAYERNORM_PARTIAL_ROWS
+ATTN_MAX_TOKENS = 81                                   # DHAUG_ATTN_MAX_TOKENS
+ATTN_MAX_HEAD_DIM = 64                                 # DHAUG_ATTN_MAX_HEAD_DIM
+ATTN_MAX_BLOCKS = 8192                                 # DHAUG_ATTN_MAX_BLOCKS
+GELU_MAX_BLOCKS = 2048                                 # DHAUG_GELU_MAX_BLOCKS
+
+
+def layernorm_workspace_doubles(C):
+    """DHAUG_LAYERNORM_WORKSPACE_DOUBLES(C)"""
+    return 2 * LAYERNORM_MAX_BLOCKS * C
+
 
 class MlpUnit(ctypes.Structure):
     """struct dhaug_mlp_unit (include/dhaug.h)"""

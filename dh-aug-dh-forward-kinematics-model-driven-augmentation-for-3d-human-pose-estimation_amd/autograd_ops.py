@@ -835,3 +835,76 @@ def graph_wcat(W):
     Wcat = GraphWcatFn.apply(W)
     Wcat._dhaug_owner = W
     return Wcat
+
+
+# ---------------------------------------------------------------------------------------------------
+# PoseFormer posenet: what lies between its dense layers.  The residual stream is fp32 in every mode; a tensor handed to a GEMM is
+# bf16 in the 'bf16' mode (out_bf16 / the type of qkv) and fp32 in the split modes.  First order only.
+# ---------------------------------------------------------------------------------------------------
+class LayerNormFn(torch.autograd.Function):
+    """y = (x - mean) rstd gamma + beta per row of x (M, C), fp32 or bf16 out.  Saved: x, gamma and the rows' mean and rstd."""
+
+    @staticmethod
+    def forward(ctx, x, gamma, beta, eps, out_bf16):
+        gd = gamma.detach()
+        y, mean, rstd = ops.layernorm_forward(x, gd, beta.detach(), eps, out_bf16=out_bf16)
+        ctx.save_for_backward(x, gd, mean, rstd)
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gy):
+        x, gamma, mean, rstd = ctx.saved_tensors
+        dx, dgamma, dbeta = ops.layernorm_backward(x, gy, gamma, mean, rstd, want_dx=ctx.needs_input_grad[0],
+                                                   want_params=ctx.needs_input_grad[1] or ctx.needs_input_grad[2],
+                                                   dx_bf16=x.dtype == BF16)
+        return dx, dgamma, dbeta, None, None
+
+
+def layer_norm(x, gamma, beta, eps=1e-5, out_bf16=False):
+    """LayerNorm over the columns of x (M, C): dhaug_layernorm_forward / _backward"""
+    return LayerNormFn.apply(x, gamma, beta, eps, out_bf16)
+
+
+class AttentionFn(torch.autograd.Function):
+    """out (S N, C) = softmax(scale q k^T) v per sequence and head of qkv (S N, 3C) = [q | k | v], in qkv's type: the qkv Linear's
+    output in place, the proj Linear's operand as it stands.  Saved: qkv (and out and the rows' log-sum-exp, which the backward entry
+    takes and does not read); P is formed again in the backward kernel."""
+
+    @staticmethod
+    def forward(ctx, qkv, S, N, H, hd, scale):
+        out, lse = ops.attn_forward(qkv, S, N, H, hd, scale)
+        ctx.save_for_backward(qkv, out, lse)
+        ctx.cfg = (S, N, H, hd, scale)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gout):
+        qkv, out, lse = ctx.saved_tensors
+        return (ops.attn_backward(qkv, out, lse, gout, *ctx.cfg),) + (None,) * 5
+
+
+def attention(qkv, S, N, H, hd, scale):
+    """multi-head attention over S sequences of N tokens: dhaug_attn_forward / _backward"""
+    return AttentionFn.apply(qkv, S, N, H, hd, scale)
+
+
+class GeluFn(torch.autograd.Function):
+    """y = z Phi(z) of the fp32 pre-activation z, fp32 or bf16 out.  Saved: z."""
+
+    @staticmethod
+    def forward(ctx, z, out_bf16):
+        ctx.save_for_backward(z)
+        return ops.gelu_forward(z, out_bf16=out_bf16)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gy):
+        z, = ctx.saved_tensors
+        return ops.gelu_backward(z, gy), None
+
+
+def gelu(z, out_bf16=False):
+    """the exact GELU: dhaug_gelu_forward / _backward"""
+    return GeluFn.apply(z, out_bf16)

@@ -1,7 +1,7 @@
 """Drop-in for R/function_baseline/model_pos_preparation.py (model_pos_preparation :18-87): builds the posenet the augmentation
-trains.  Of the reference's five posenet names this package implements four, each through a factory of its own: `videopose` (the
+trains.  This package implements the reference's five posenet names, each through a factory of its own: `videopose` (the
 default run's single-frame model, model_pos_preparation), `mulit_farme_videopose` (multi_frame_model_pos_preparation), `gcn`
-(gcn_model_pos_preparation) and `mlp` (mlp_model_pos_preparation).  `mulit_farme_poseformer` is not implemented."""
+(gcn_model_pos_preparation), `mlp` (mlp_model_pos_preparation) and `mulit_farme_poseformer` (poseformer_model_pos_preparation)."""
 import torch
 
 from ..models_baseline.videopose.model_VideoPose3D import TemporalModelOptimized1f
@@ -98,3 +98,33 @@ def mlp_model_pos_preparation(args, dataset, device, flag='train'):
         model_pos.apply(init_weights)
     model_pos = model_pos.to(device)
     return _finish(args, name, model_pos, device, "%s: %d stages" % (name, int(args.stages)))
+
+
+POSEFORMER_POSENETS = ("mulit_farme_poseformer",)
+
+
+def poseformer_model_pos_preparation(args, dataset, device, flag='train'):
+    """the reference's `mulit_farme_poseformer` branch (R/function_baseline/model_pos_preparation.py:51-63): the PoseFormer posenet
+    (B, T, J, 2) -> (B, 1, J, 3), PoseTransformer(num_frame = the receptive field of args.architecture, num_joints from
+    dataset.skeleton() where the dataset has one and 16 otherwise, in_chans=2, embed_dim_ratio=32, depth=4, num_heads=8, mlp_ratio=2.,
+    qkv_bias=True, qk_scale=None) with drop_path_rate 0.1 for flag 'train' and 0 for 'test'.  Without args.pretrain the nn.Linear
+    weights are init_weights' (kaiming_normal_), drawn on the HOST generator before the move to `device`, as in
+    mlp_model_pos_preparation.  A factory of its own: the four above keep refusing this name."""
+    from ..models_baseline.mlp import init_weights
+    from ..models_baseline.poseformer import PoseTransformer
+    from ..models_Fk_GAN.video_mode_operate import video_receptive_field
+    name = args.posenet_name
+    if name not in POSEFORMER_POSENETS:
+        raise NotImplementedError("posenet_name %r is not a transformer posenet of this package; implemented: %s"
+                                  % (name, ", ".join(POSEFORMER_POSENETS)))
+    if flag not in ("train", "test"):
+        raise ValueError("flag must be 'train' or 'test', got %r" % (flag,))
+    receptive_field = video_receptive_field([int(w) for w in str(args.architecture).split(',')])
+    skeleton = getattr(dataset, "skeleton", None)
+    num_joints = skeleton().num_joints() if callable(skeleton) else 16
+    model_pos = PoseTransformer(num_frame=receptive_field, num_joints=num_joints, in_chans=2, embed_dim_ratio=32, depth=4, num_heads=8,
+                                mlp_ratio=2., qkv_bias=True, qk_scale=None, drop_path_rate=0.1 if flag == "train" else 0)
+    if not getattr(args, "pretrain", False):
+        model_pos.apply(init_weights)
+    model_pos = model_pos.to(device)
+    return _finish(args, name, model_pos, device, "%s (%s): %d frames, %d joints" % (name, flag, receptive_field, num_joints))

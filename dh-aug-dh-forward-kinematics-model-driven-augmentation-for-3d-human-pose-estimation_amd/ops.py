@@ -1432,3 +1432,175 @@ def graph_wcat(src, to_cat=True):
         dst = torch.empty((2, n_in, n_out), dtype=torch.float32, device=s.device)
     _lib.call("dhaug_graph_wcat", _p(s), _p(dst), n_in, n_out, int(bool(to_cat)), _stream())
     return dst
+
+
+# ---------------------------------------------------------------------------------------------- PoseFormer posenet: LayerNorm, attention, GELU
+def _vec_rows(t, width, name, what, dtypes=(torch.float32, BF16)):
+    """a (M, >= width) matrix the vector kernels read where it lies: contiguous rows, base and pitch on the 4-element grid (a view
+    that is not is copied): (tensor, row pitch)"""
+    if not t.is_cuda:
+        raise RuntimeError("dhaug op `%s` needs a GPU tensor (no CPU fallback exists)" % name)
+    if t.dim() != 2 or t.shape[1] < width or t.dtype not in dtypes:
+        raise ValueError("%s: %s must be a %s (M, >= %d) matrix, got %s %s"
+                         % (name, what, " or ".join(str(d) for d in dtypes), width, t.dtype, tuple(t.shape)))
+    if t.stride(1) != 1 or t.stride(0) < width or t.stride(0) % 4 or t.data_ptr() % (8 if t.dtype == BF16 else 16):
+        if t.shape[1] % 4:
+            raise ValueError("%s: %s has rows off the 4-element grid (pitch %d)" % (name, what, t.shape[1]))
+        t = t.contiguous()
+        if t.data_ptr() % 16:
+            t = t.clone()
+    return t, t.stride(0)
+
+
+def _vec_param(t, n, name, what):
+    if not (t.is_cuda and t.dtype == torch.float32 and t.numel() == n and t.is_contiguous()):
+        raise ValueError("%s: %s must be a contiguous fp32 device tensor of %d elements" % (name, what, n))
+    return t
+
+
+def _check_layernorm_cols(C, name):
+    if C < 16 or C % 16 or C > _lib.LAYERNORM_MAX_COLS:
+        raise ValueError("%s: C must be a multiple of 16 up to %d (DHAUG_LAYERNORM_MAX_COLS), got %d" % (name, _lib.LAYERNORM_MAX_COLS, C))
+
+
+def layernorm_forward(x, gamma, beta, eps=1e-5, out_bf16=False, want_stats=True, out=None):
+    """dhaug_layernorm_forward: x fp32 or bf16 (M, >= C), C = gamma.numel() -> (y fp32 or bf16 (M, C), mean, rstd) (the statistics fp32
+    (M,), None without want_stats).  out: write y into this matrix (any pitch >= C; no column beyond C is touched)."""
+    name = "layernorm_forward"
+    C = gamma.numel()
+    _check_layernorm_cols(C, name)
+    x, ld_x = _vec_rows(x, C, name, "x")
+    gamma, beta = _vec_param(gamma, C, name, "gamma"), _vec_param(beta, C, name, "beta")
+    M = x.shape[0]
+    if out is None:
+        out = torch.empty((M, C), dtype=BF16 if out_bf16 else torch.float32, device=x.device)
+    y, ld_y = _vec_rows(out, C, name, "out")
+    if y is not out or y.shape[0] != M:
+        raise ValueError("layernorm_forward: out must be a (%d, >= %d) matrix with rows on the 4-element grid" % (M, C))
+    mean = torch.empty((M,), dtype=torch.float32, device=x.device) if want_stats else None
+    rstd = torch.empty((M,), dtype=torch.float32, device=x.device) if want_stats else None
+    _lib.call("dhaug_layernorm_forward", _p(x), int(x.dtype == BF16), ld_x, _p(gamma), _p(beta), float(eps), _p(y), int(y.dtype == BF16),
+              ld_y, _p(mean), _p(rstd), M, C, _stream())
+    return out, mean, rstd
+
+
+def layernorm_backward(x, g, gamma, mean, rstd, want_dx=True, want_params=True, dx_bf16=False, workspace=None):
+    """dhaug_layernorm_backward: (dx fp32 or bf16 (M, C) or None, dgamma, dbeta fp32 (C,) or None); the parameter gradients are fp64
+    column sums in a fixed order through a workspace of _lib.layernorm_workspace_doubles(C) doubles"""
+    name = "layernorm_backward"
+    C = gamma.numel()
+    _check_layernorm_cols(C, name)
+    x, ld_x = _vec_rows(x, C, name, "x")
+    g, ld_g = _vec_rows(g, C, name, "g")
+    M = x.shape[0]
+    if g.shape[0] != M or mean.numel() != M or rstd.numel() != M:
+        raise ValueError("layernorm_backward: x, g, mean and rstd differ in rows")
+    gamma, mean, rstd = _vec_param(gamma, C, name, "gamma"), _vec_param(mean, M, name, "mean"), _vec_param(rstd, M, name, "rstd")
+    dx = torch.empty((M, C), dtype=BF16 if dx_bf16 else torch.float32, device=x.device) if want_dx else None
+    dgamma = dbeta = ws = None
+    if want_params:
+        dgamma = torch.empty((C,), dtype=torch.float32, device=x.device)
+        dbeta = torch.empty((C,), dtype=torch.float32, device=x.device)
+        ws = workspace if workspace is not None else torch.empty(_lib.layernorm_workspace_doubles(C), dtype=torch.float64, device=x.device)
+        assert ws.is_cuda and ws.dtype == torch.float64 and ws.numel() >= _lib.layernorm_workspace_doubles(C)
+    _lib.call("dhaug_layernorm_backward", _p(x), int(x.dtype == BF16), ld_x, _p(g), int(g.dtype == BF16), ld_g, _p(gamma), _p(mean),
+              _p(rstd), _p(dx), int(dx_bf16), C, _p(dgamma), _p(dbeta), _p(ws), M, C, _stream())
+    return dx, dgamma, dbeta
+
+
+def _check_attn(S, N, H, hd, name):
+    if not 1 <= N <= _lib.ATTN_MAX_TOKENS:
+        raise ValueError("%s: sequences of 1 to %d tokens (DHAUG_ATTN_MAX_TOKENS), got %d" % (name, _lib.ATTN_MAX_TOKENS, N))
+    if hd % 4 or not 4 <= hd <= _lib.ATTN_MAX_HEAD_DIM:
+        raise ValueError("%s: the head width must be a multiple of 4 from 4 to %d (DHAUG_ATTN_MAX_HEAD_DIM), got %d"
+                         % (name, _lib.ATTN_MAX_HEAD_DIM, hd))
+    if S < 0 or H < 1:
+        raise ValueError("%s: S >= 0 sequences and H >= 1 heads, got %d and %d" % (name, S, H))
+
+
+def attn_forward(qkv, S, N, H, hd, scale, out_bf16=None, want_lse=True, out=None):
+    """dhaug_attn_forward: qkv fp32 or bf16 (S N, >= 3 H hd) = [q | k | v], head h in columns [h hd, (h + 1) hd) of each third ->
+    (out (S N, H hd) = softmax(scale q k^T) v per sequence and head, lse fp32 (S, H, N) or None).  By default out has qkv's type."""
+    name = "attn_forward"
+    _check_attn(S, N, H, hd, name)
+    C = H * hd
+    qkv, ld = _vec_rows(qkv, 3 * C, name, "qkv")
+    if qkv.shape[0] != S * N:
+        raise ValueError("attn_forward: qkv must hold S N = %d rows, got %d" % (S * N, qkv.shape[0]))
+    if out is None:
+        out_bf16 = (qkv.dtype == BF16) if out_bf16 is None else bool(out_bf16)
+        out = torch.empty((S * N, C), dtype=BF16 if out_bf16 else torch.float32, device=qkv.device)
+    o, ld_o = _vec_rows(out, C, name, "out")
+    if o is not out or o.shape[0] != S * N:
+        raise ValueError("attn_forward: out must be a (%d, >= %d) matrix with rows on the 4-element grid" % (S * N, C))
+    lse = torch.empty((S, H, N), dtype=torch.float32, device=qkv.device) if want_lse else None
+    _lib.call("dhaug_attn_forward", _p(qkv), int(qkv.dtype == BF16), ld, _p(o), int(o.dtype == BF16), ld_o, _p(lse), S, N, H, hd,
+              float(scale), _stream())
+    return out, lse
+
+
+def attn_backward(qkv, out, lse, dout, S, N, H, hd, scale, dqkv_bf16=None, dqkv=None):
+    """dhaug_attn_backward: the whole (S N, 3 H hd) cotangent of qkv = [dq | dk | dv] (by default of qkv's type) from qkv and the
+    cotangent dout of out; the forward's out and lse are part of the entry's signature and checked, the kernel forms P again
+    from qkv and reads neither (include/dhaug.h)"""
+    name = "attn_backward"
+    _check_attn(S, N, H, hd, name)
+    C = H * hd
+    qkv, ld = _vec_rows(qkv, 3 * C, name, "qkv")
+    out, ld_o = _vec_rows(out, C, name, "out")
+    dout, ld_d = _vec_rows(dout, C, name, "dout")
+    if not (qkv.shape[0] == out.shape[0] == dout.shape[0] == S * N):
+        raise ValueError("attn_backward: qkv, out and dout must hold S N = %d rows" % (S * N))
+    lse = _vec_param(lse, S * H * N, name, "lse")
+    if dqkv is None:
+        dqkv_bf16 = (qkv.dtype == BF16) if dqkv_bf16 is None else bool(dqkv_bf16)
+        dqkv = torch.empty((S * N, 3 * C), dtype=BF16 if dqkv_bf16 else torch.float32, device=qkv.device)
+    d, ld_q = _vec_rows(dqkv, 3 * C, name, "dqkv")
+    if d is not dqkv or d.shape[0] != S * N:
+        raise ValueError("attn_backward: dqkv must be a (%d, >= %d) matrix with rows on the 4-element grid" % (S * N, 3 * C))
+    _lib.call("dhaug_attn_backward", _p(qkv), int(qkv.dtype == BF16), ld, _p(out), int(out.dtype == BF16), ld_o, _p(lse), _p(dout),
+              int(dout.dtype == BF16), ld_d, _p(d), int(d.dtype == BF16), ld_q, S, N, H, hd, float(scale), _stream())
+    return dqkv
+
+
+def _gelu_rows(t, name, what, dtypes):
+    """(tensor, M, C, pitch) of a vector or matrix for the GELU kernels: contiguous data is one row (no rule on its length)"""
+    if not t.is_cuda:
+        raise RuntimeError("dhaug op `%s` needs a GPU tensor (no CPU fallback exists)" % name)
+    if t.dtype not in dtypes or t.dim() not in (1, 2):
+        raise ValueError("%s: %s must be a %s vector or matrix, got %s %s" % (name, what, " or ".join(str(d) for d in dtypes), t.dtype, tuple(t.shape)))
+    if t.dim() == 2 and t.stride(1) == 1 and t.stride(0) % 4 == 0 and t.stride(0) >= t.shape[1] and t.shape[1] % 4 == 0 \
+            and 0 < t.shape[1] < (1 << 28) \
+            and t.data_ptr() % (8 if t.dtype == BF16 else 16) == 0:
+        return t, t.shape[0], t.shape[1], t.stride(0)
+    if not t.is_contiguous():
+        t = t.contiguous()
+    if t.data_ptr() % 16:
+        t = t.clone()
+    if t.numel() >= (1 << 28):
+        raise ValueError("%s: %s: %d contiguous elements whose rows are off the 4-element grid" % (name, what, t.numel()))
+    return t, 1, t.numel(), t.numel()
+
+
+def gelu_forward(z, out_bf16=False):
+    """dhaug_gelu_forward: y = z Phi(z) (the exact GELU) of a fp32 vector or matrix, fp32 or bf16, in z's shape"""
+    zz, M, C, ld = _gelu_rows(z, "gelu_forward", "z", (torch.float32,))
+    y = torch.empty(z.shape, dtype=BF16 if out_bf16 else torch.float32, device=z.device)
+    _lib.call("dhaug_gelu_forward", _p(zz), ld, _p(y), int(out_bf16), C if M > 1 else y.numel(), M, C, _stream())
+    return y
+
+
+def gelu_backward(z, g, out_bf16=False):
+    """dhaug_gelu_backward: dz = g (Phi(z) + z phi(z)), g fp32 or bf16 in z's shape, dz fp32 or bf16"""
+    name = "gelu_backward"
+    if tuple(g.shape) != tuple(z.shape):
+        raise ValueError("gelu_backward: z and g differ in shape, %s and %s" % (tuple(z.shape), tuple(g.shape)))
+    zz, M, C, ld = _gelu_rows(z, name, "z", (torch.float32,))
+    gg, Mg, Cg, ld_g = _gelu_rows(g, name, "g", (torch.float32, BF16))
+    if (Mg, Cg) != (M, C):                       # (one of the two is a strided view, the other one row: both as one row)
+        zz, M, C, ld = _gelu_rows(z.contiguous().view(-1), name, "z", (torch.float32,))
+        gg, Mg, Cg, ld_g = _gelu_rows(g.contiguous().view(-1), name, "g", (torch.float32, BF16))
+    dz = torch.empty(z.shape, dtype=BF16 if out_bf16 else torch.float32, device=z.device)
+    _lib.call("dhaug_gelu_backward", _p(zz), ld, _p(gg), int(gg.dtype == BF16), ld_g, _p(dz), int(out_bf16),
+              C if M > 1 else dz.numel(), M, C, _stream())
+    return dz

@@ -1027,6 +1027,73 @@ int dhaug_graph_adj_grad(const void* g, int g_bf16, int64_t ld_g, const void* h,
                          int nnz, float* dA, void* workspace, int64_t M, int64_t C, void* stream);
 int dhaug_graph_wcat(const float* src, float* dst, int64_t in, int64_t out, int to_cat, void* stream);
 
+/* ------------------------------------------------------------------------------------------------------
+ * PoseFormer posenet: LayerNorm, short-sequence attention, exact GELU (R/models_baseline/poseformer/model_poseformer.py;
+ * csrc/dhaug_attn.hip)
+ * ----------------------------------------------------------------------------------------------------
+ * Activations are rows; every tensor has a row pitch (ld, in elements).  A tensor with a *_bf16 flag is fp32 (0) or bf16 (1); an
+ * output is rounded once from the fp32 result.  Arithmetic is fp32 (fp64 for the LayerNorm parameter gradients' column sums).  No
+ * entry reads or writes a column at or beyond the stated width.  Vector stores, no atomics, every sum in a fixed order: two calls on
+ * the same inputs give the same bits.
+ * ALIGNMENT of a row tensor: base on 16 bytes (fp32) or 8 bytes (bf16), ld a multiple of 4: rows are read and written as 4-element
+ *   vectors.  gamma, beta, mean, rstd, lse, dgamma, dbeta: 4 bytes (read and written element by element: parameters may lie on any
+ *   4-byte boundary of PosenetAdam's flat buffer).  DHAUG_EALIGN otherwise, and for a pitch below the tensor's width.
+ *
+ * dhaug_layernorm_forward: x (M, ld_x >= C) -> y (M, ld_y >= C), y = (x - mean) * rstd * gamma + beta per row, rstd = 1 / sqrt(var +
+ *   eps), var the mean of the squared CENTRED values (the row is held in registers: one read), mean = m0 + sum(x - m0) / C with m0 =
+ *   sum(x) / C -- a constant row has mean = its constant and y = beta exactly; the centred values x - mean are centred once more
+ *   (their own mean is what fp32 cannot hold of the row's: a row of 1 000 + N(0, 1e-3) keeps its variance).  mean, rstd: M fp32 each, written for the backward
+ *   pass; either may be NULL (evaluation).  DHAUG_EUNSUPPORTED: C % 16 != 0 or C > DHAUG_LAYERNORM_MAX_COLS.
+ * dhaug_layernorm_backward: from x, the cotangent g (M, ld_g >= C), gamma and the forward's mean and rstd:
+ *     dx = rstd * (g gamma - mean_c(g gamma) - xhat mean_c(g gamma xhat)),  xhat = (x - mean) rstd      (dx NULL: not computed)
+ *     dgamma[c] = sum_r g[r,c] xhat[r,c],  dbeta[c] = sum_r g[r,c]                                       (both NULL: not computed)
+ *   The column sums run in fp64 in two stages: up to DHAUG_LAYERNORM_MAX_BLOCKS workgroups each walk a slice of the rows with
+ *   DHAUG_LAYERNORM_PARTIAL_ROWS (C <= 32) or half as many row lanes per column and write their partials to workspace (device,
+ *   DHAUG_LAYERNORM_WORKSPACE_DOUBLES(C) doubles, 8-byte aligned, one call at a time per workspace); a second launch adds them in
+ *   workgroup order and rounds once.  M = 0 writes zeros.  The same limits on C.
+ * dhaug_attn_forward: qkv (S N, ld_qkv >= 3C), C = H hd: the output of the qkv Linear for S sequences of N tokens, columns [0, C) q,
+ *   [C, 2C) k, [2C, 3C) v, head h in columns [h hd, (h + 1) hd) of each third.  Per sequence and head P = softmax(scale q k^T) over
+ *   the N keys (row maximum subtracted before exp: scores of any finite size give finite results), out[:, h hd ...] = P v, out
+ *   (S N, ld_out >= C): the operand of the proj Linear.  lse (S H N fp32, [(s H + h) N + i], may be NULL): the rows' log-sum-exp of
+ *   the scaled scores.  Keys are summed in ascending order.  DHAUG_EUNSUPPORTED (no launch): N outside [1, DHAUG_ATTN_MAX_TOKENS],
+ *   hd outside [4, DHAUG_ATTN_MAX_HEAD_DIM] or hd % 4 != 0.  Any S, H >= 0 (0: a no-op that looks at no pointer).
+ * dhaug_attn_backward: from qkv and the cotangent dout (S N, ld_dout >= C) of out: dqkv (S N, ld_dqkv >= 3C), all of columns [0, 3C)
+ *   written -- dq, dk, dv each in its third: the incoming gradient of the qkv Linear as it stands.  P is never stored in global
+ *   memory: the kernel forms it again exactly as the forward pass did (the same scores, their maximum, exp, the sum).  out and lse
+ *   are checked like the other arguments and NOT read: exp(score - lse) would carry the rounding of lse (half an ulp of a number the
+ *   size of the largest score: 4e-6 at scores of 80) into every weight, and D = dout . out would not cancel the rounding of dP where
+ *   P is peaked; both were measured above the bound of tests/test_gpu_attn_kernels.py.
+ *     dP_ij = dout_i . v_j,  D_i = sum_j P_ij dP_ij,  dS_ij = P_ij (dP_ij - D_i),  dq_i = scale sum_j dS_ij k_j,  dk_j = scale sum_i dS_ij q_i,
+ *     dv_j = sum_i P_ij dout_i                                                              (j and i ascending).
+ *   dqkv must not alias qkv (DHAUG_EINVAL).  The same limits.
+ * dhaug_gelu_forward: y = z Phi(z), Phi the normal distribution function by erfc (the exact form, not tanh), z fp32 (M, ld_z >= C)
+ *   -- the pre-activation a GEMM wrote, bias included -- y (M, ld_y >= C) fp32 or bf16.  Any C >= 1 (the C % 4 columns behind the last
+ *   vector go element by element); M = 1 lifts the rule on the pitches.
+ * dhaug_gelu_backward: dz = g (Phi(z) + z phi(z)), g (M, ld_g >= C) fp32 or bf16, dz fp32 or bf16.
+ *   Both take at most DHAUG_GELU_MAX_BLOCKS workgroups of 256 four-column items: more items, more passes per thread.
+ * All: DHAUG_EINVAL for a negative size, a flag outside {0, 1}, a NULL required pointer. */
+#define DHAUG_LAYERNORM_MAX_COLS 2048
+#define DHAUG_LAYERNORM_MAX_BLOCKS 256
+#define DHAUG_LAYERNORM_PARTIAL_ROWS 8
+#define DHAUG_LAYERNORM_WORKSPACE_DOUBLES(C) (2LL * DHAUG_LAYERNORM_MAX_BLOCKS * (C))
+#define DHAUG_ATTN_MAX_TOKENS 81
+#define DHAUG_ATTN_MAX_HEAD_DIM 64
+#define DHAUG_ATTN_MAX_BLOCKS 8192
+#define DHAUG_GELU_MAX_BLOCKS 2048
+int dhaug_layernorm_forward(const void* x, int x_bf16, int64_t ld_x, const float* gamma, const float* beta, float eps, void* y,
+                            int y_bf16, int64_t ld_y, float* mean, float* rstd, int64_t M, int64_t C, void* stream);
+int dhaug_layernorm_backward(const void* x, int x_bf16, int64_t ld_x, const void* g, int g_bf16, int64_t ld_g, const float* gamma,
+                             const float* mean, const float* rstd, void* dx, int dx_bf16, int64_t ld_dx, float* dgamma,
+                             float* dbeta, void* workspace, int64_t M, int64_t C, void* stream);
+int dhaug_attn_forward(const void* qkv, int qkv_bf16, int64_t ld_qkv, void* out, int out_bf16, int64_t ld_out, float* lse,
+                       int64_t S, int N, int H, int hd, float scale, void* stream);
+int dhaug_attn_backward(const void* qkv, int qkv_bf16, int64_t ld_qkv, const void* out, int out_bf16, int64_t ld_out,
+                        const float* lse, const void* dout, int dout_bf16, int64_t ld_dout, void* dqkv, int dqkv_bf16,
+                        int64_t ld_dqkv, int64_t S, int N, int H, int hd, float scale, void* stream);
+int dhaug_gelu_forward(const float* z, int64_t ld_z, void* y, int y_bf16, int64_t ld_y, int64_t M, int64_t C, void* stream);
+int dhaug_gelu_backward(const float* z, int64_t ld_z, const void* g, int g_bf16, int64_t ld_g, void* dz, int dz_bf16, int64_t ld_dz,
+                        int64_t M, int64_t C, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
