@@ -37,6 +37,8 @@ SIGNATURES = {
     "dhaug_pose_mpjpe": [_vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp],
     "dhaug_grad_sumsq": [_vp, _i64, _f32, _vp, _vp, _vp],
     "dhaug_adam_clip_step": [_vp, _vp, _vp, _vp, _i64, _f32, _f32, _f32, _f32, _vp, _f32, _f32, _vp, _vp, _vp],
+    "dhaug_adam_clip_step_lr": [_vp, _vp, _vp, _vp, _i64, _vp, _f32, _f32, _f32, _vp, _f32, _f32, _vp, _vp, _vp],
+    "dhaug_u64_add": [_vp, _u64, _vp],
     "dhaug_gemm_bf16_dmask": [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _i32, _f32, _vp, _i64, _i64, _i64, _i64, _vp],
     "dhaug_gemm_bf16_dmask_pad": [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _i32, _f32, _vp, _i64, _i64, _i64, _i64, _i64, _vp],
     "dhaug_gemm_bf16_dbits": [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _i32, _f32, _vp, _i64, _i64, _vp],
@@ -84,6 +86,11 @@ SIGNATURES = {
     "dhaug_bn_act_backward_partials": [_vp, _i32, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _f32, _u64, _u64, _i64, _i64, _vp, _vp],
     "dhaug_bn_act_backward": [_vp, _i32, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _f32, _u64, _u64, _vp, _vp, _i64, _vp, _i64, _vp,
                               _vp, _i64, _i64, _vp],
+    "dhaug_bn_act_forward_dr": [_vp, _i32, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f32, _f32, _f32, _vp, _u64,
+                                _vp, _i64, _vp, _i64, _i64, _i64, _vp],
+    "dhaug_bn_act_backward_partials_dr": [_vp, _i32, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _f32, _vp, _u64, _i64, _i64, _vp, _vp],
+    "dhaug_bn_act_backward_dr": [_vp, _i32, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _f32, _vp, _u64, _vp, _vp, _i64, _vp, _i64, _vp,
+                                 _vp, _i64, _i64, _vp],
     "dhaug_bn_fold": [_vp, _i64, _vp, _vp, _vp, _vp, _f32, _vp, _i64, _vp, _vp, _i64, _i64, _vp],
     "dhaug_bn_fold_bias": [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _f32, _vp, _i64, _vp, _vp, _i64, _i64, _vp],
     "dhaug_conv_taps_pack_bf16": [_vp, _i64, _i64, _i32, _vp, _i64, _vp, _i64, _vp],

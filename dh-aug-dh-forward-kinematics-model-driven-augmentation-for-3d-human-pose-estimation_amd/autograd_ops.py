@@ -634,9 +634,43 @@ def center_flip(x, center=False, flip=False):
 # ---------------------------------------------------------------------------------------------------
 # posenet: BatchNorm1d (batch statistics) + ReLU + Dropout (+ residual) between two dense layers
 # ---------------------------------------------------------------------------------------------------
+class DeviceDropoutStream:
+    """The dropout stream of a replayable training step: the position lives on the device.  cell: int64 (2,) {seed, base}, seeded
+    from the torch generator's (initial_seed, get_offset()).  The k-th dropout call since the stream was opened is handed
+    (cell, 4 k); the kernels add the delta to the base themselves (the _dr entries), and the owner advances the base by 4 K once
+    per step, behind the backward pass (advance) -- so the k-th call of step s gets the offset start + 4 (K s + k), the one the
+    eager path's host-side bookkeeping would have given it.  calls counts on the host (captured or replayed steps add theirs)."""
+
+    def __init__(self, cell):
+        self.cell = cell
+        self.calls = 0            # dropout calls issued since the stream was opened, replayed ones included
+        self.k = 0                # ... of the step being built
+
+    def next(self):
+        k = self.k
+        self.k += 1
+        self.calls += 1
+        return self.cell, 4 * k
+
+    def advance(self):
+        """end of a step: one launch moves the base past this step's K calls; returns K"""
+        K, self.k = self.k, 0
+        if K:
+            ops.u64_add(self.cell[1:2], 4 * K)
+        return K
+
+
+# Set while a step draws its masks from a device stream (function_aug.model_pos_train.StepRunner with graph=True), None otherwise:
+# a module-level switch like CAPTURE_ID, because the layers that call dropout_stream know nothing of who runs them.
+DEVICE_DROPOUT = None
+
+
 def dropout_stream(device):
     """(seed, offset) of the device generator for an in-kernel Philox dropout mask, as Fk_generator._jitter_stream: the offset
-    advances per call (layers get independent masks) and torch.manual_seed reproduces a run"""
+    advances per call (layers get independent masks) and torch.manual_seed reproduces a run.  While DEVICE_DROPOUT is set:
+    (cell, delta) of that stream, and the torch generator is not touched."""
+    if DEVICE_DROPOUT is not None:
+        return DEVICE_DROPOUT.next()
     g = torch.cuda.default_generators[device.index if device.index is not None else torch.cuda.current_device()]
     off = g.get_offset()
     g.set_offset(off + 4)
@@ -646,7 +680,8 @@ def dropout_stream(device):
 class BnActFn(torch.autograd.Function):
     """y = dropout_p(relu(batchnorm(z))) (+ residual), batch statistics, the module's running buffers updated in the same launch.
     z: fp32 (M, C) or bf16 (M, ceil16 C) -- the output (and the residual) has z's type.  Saved: z, mean, rstd, gamma, beta and the
-    mask's (seed, offset); no mask tensor.  First order only."""
+    mask's (seed, offset) -- or the (cell, delta) a device stream handed out, so that the backward pass reads the same cell with the
+    same delta; no mask tensor.  First order only."""
 
     @staticmethod
     def forward(ctx, z, gamma, beta, residual, bn_buffers, momentum, eps, p):

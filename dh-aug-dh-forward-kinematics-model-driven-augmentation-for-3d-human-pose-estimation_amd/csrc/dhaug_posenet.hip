@@ -11,6 +11,9 @@
 //                                  for the backward pass and updates running_mean / running_var / num_batches_tracked as nn.BatchNorm1d.
 //  dhaug_bn_act_backward_partials  gz = g * keep / (1 - p) * [pre-activation > 0]: sum gz and sum gz * xhat per column and chunk, fp64.
 //  dhaug_bn_act_backward           dz = gamma * rstd * (gz - sum gz / M - xhat * sum(gz xhat) / M); chunk 0 writes dgamma, dbeta.
+//  dhaug_bn_act_forward_dr, dhaug_bn_act_backward_partials_dr, dhaug_bn_act_backward_dr
+//                                  the three kernels above instantiated with DR = true: (seed, offset) = (cell[0], cell[1] + delta) read from
+//                                  device memory, so a launch captured in a hipGraph draws a new mask at every replay.
 //  dhaug_bn_fold                   W' = gamma * rstd_run (.) rows of W, b' = beta - running_mean * gamma * rstd_run.
 //  dhaug_bn_fold_bias              the same for a layer with a bias b of its own (R/models_baseline/mlp/linear_model.py: nn.Linear in
 //                                  front of every BatchNorm): b' = beta + (b - running_mean) * gamma * rstd_run.
@@ -117,7 +120,20 @@ struct Drop {
     unsigned long long seed, offset;
     unsigned thresh;            // (uint32)(p * 2^32); 0: no dropout, no random numbers
     float inv_keep;             // 1 / (1 - p)
+    const unsigned long long* cell;   // the _dr entries: device words {seed, base}; `offset` then holds the call's delta
 };
+
+// The stream position of this launch.  DR = false: the immediates of the launch.  DR = true (the _dr entries, replayable in a captured
+// graph): seed = cell[0], offset = cell[1] + delta, a full 64-bit sum; the cell is not read where there is no dropout.
+template <bool DR>
+__device__ __forceinline__ Drop drop_here(const Drop& d) {
+    Drop o = d;
+    if (DR && d.thresh) {
+        o.seed = d.cell[0];
+        o.offset = d.cell[1] + d.offset;
+    }
+    return o;
+}
 
 // keep decisions of the N elements (row, col ..): counter = (element index / 4, offset), element index = row * C + col; the four words
 // of one call decide four consecutive elements; keep iff word >= thresh
@@ -263,7 +279,7 @@ struct ColConst {
     float mean[SC], rstd[SC], gamma[SC], beta[SC];
 };
 
-template <typename T>
+template <typename T, bool DR>
 __global__ __launch_bounds__(kBlock) void bn_act_forward_kernel(FwdArgs a) {
     constexpr int N = VecOf<T>::N, SC = kLanesPerRow * N;
     __shared__ ColConst<SC> cc;
@@ -313,7 +329,7 @@ __global__ __launch_bounds__(kBlock) void bn_act_forward_kernel(FwdArgs a) {
     if (col >= Cp) return;
     const T* z = reinterpret_cast<const T*>(a.c.z);
     const T* res = reinterpret_cast<const T*>(a.res);
-    const Drop d = a.c.drop;
+    const Drop d = drop_here<DR>(a.c.drop);
     for (long long r = r0 + (threadIdx.x >> 3); r < r1; r += kRowsPerPass) {
         float y[N];
         if (col < C) {
@@ -341,24 +357,24 @@ __global__ __launch_bounds__(kBlock) void bn_act_forward_kernel(FwdArgs a) {
 
 // gz of one vector: g * keep / (1 - p) where the pre-activation is > 0, else exactly 0; xhat alongside
 template <typename T, int N>
-__device__ __forceinline__ void gz_of_row(const Common& c, const T* __restrict__ g, long long ld_g, const float* mean, const float* rstd,
+__device__ __forceinline__ void gz_of_row(const Common& c, const Drop& d, const T* __restrict__ g, long long ld_g, const float* mean, const float* rstd,
                                           const float* gamma, const float* beta, long long r, long long col, float (&gz)[N],
                                           float (&xh)[N]) {
     float v[N], gv[N];
     bool keep[N];
     load_row(reinterpret_cast<const T*>(c.z) + r * c.ld_z + col, col, c.C, v);
     load_row(g + r * ld_g + col, col, c.C, gv);
-    if (c.drop.thresh) keep_mask<N>(c.drop, r, col, c.C, keep);
+    if (d.thresh) keep_mask<N>(d, r, col, c.C, keep);
 #pragma unroll
     for (int j = 0; j < N; ++j) {
         const float pre = bn_pre(v[j], mean[j], rstd[j], gamma[j], beta[j], xh[j]);
         float t = pre > 0.0f ? gv[j] : 0.0f;
-        if (c.drop.thresh) t = keep[j] ? t * c.drop.inv_keep : 0.0f;
+        if (d.thresh) t = keep[j] ? t * d.inv_keep : 0.0f;
         gz[j] = t;
     }
 }
 
-template <typename T>
+template <typename T, bool DR>
 __global__ __launch_bounds__(kBlock) void bn_act_backward_partials_kernel(BwdArgs a) {
     constexpr int N = VecOf<T>::N, SC = kLanesPerRow * N;
     __shared__ ColConst<SC> cc;
@@ -375,13 +391,14 @@ __global__ __launch_bounds__(kBlock) void bn_act_backward_partials_kernel(BwdArg
     const long long col = c0 + lc;
     const long long r0 = (long long)blockIdx.y * a.c.rows_per_chunk;
     const long long r1 = r0 + a.c.rows_per_chunk < M ? r0 + a.c.rows_per_chunk : M;
+    const Drop d = drop_here<DR>(a.c.drop);
     double s[N], q[N];
 #pragma unroll
     for (int j = 0; j < N; ++j) s[j] = q[j] = 0.0;
     if (col < C) {
         for (long long r = r0 + (threadIdx.x >> 3); r < r1; r += kRowsPerPass) {
             float gz[N], xh[N];
-            gz_of_row<T, N>(a.c, reinterpret_cast<const T*>(a.g), a.ld_g, cc.mean + lc, cc.rstd + lc, cc.gamma + lc, cc.beta + lc, r, col,
+            gz_of_row<T, N>(a.c, d, reinterpret_cast<const T*>(a.g), a.ld_g, cc.mean + lc, cc.rstd + lc, cc.gamma + lc, cc.beta + lc, r, col,
                             gz, xh);
 #pragma unroll
             for (int j = 0; j < N; ++j) {
@@ -393,7 +410,7 @@ __global__ __launch_bounds__(kBlock) void bn_act_backward_partials_kernel(BwdArg
     write_partials<N>(s, q, lds, col, C, a.ws);
 }
 
-template <typename T>
+template <typename T, bool DR>
 __global__ __launch_bounds__(kBlock) void bn_act_backward_kernel(BwdArgs a) {
     constexpr int N = VecOf<T>::N, SC = kLanesPerRow * N;
     __shared__ ColConst<SC> cc;
@@ -426,11 +443,12 @@ __global__ __launch_bounds__(kBlock) void bn_act_backward_kernel(BwdArgs a) {
     const long long r0 = (long long)blockIdx.y * a.c.rows_per_chunk;
     const long long r1 = r0 + a.c.rows_per_chunk < M ? r0 + a.c.rows_per_chunk : M;
     if (col >= Cp) return;
+    const Drop d = drop_here<DR>(a.c.drop);
     for (long long r = r0 + (threadIdx.x >> 3); r < r1; r += kRowsPerPass) {
         float dz[N];
         if (col < C) {
             float gz[N], xh[N];
-            gz_of_row<T, N>(a.c, reinterpret_cast<const T*>(a.g), a.ld_g, cc.mean + lc, cc.rstd + lc, cc.gamma + lc, cc.beta + lc, r, col,
+            gz_of_row<T, N>(a.c, d, reinterpret_cast<const T*>(a.g), a.ld_g, cc.mean + lc, cc.rstd + lc, cc.gamma + lc, cc.beta + lc, r, col,
                             gz, xh);
 #pragma unroll
             for (int j = 0; j < N; ++j) dz[j] = (cc.gamma[lc + j] * cc.rstd[lc + j]) * ((gz[j] - c1s[lc + j]) - xh[j] * c2s[lc + j]);
@@ -514,12 +532,23 @@ inline bool rows_ok(const void* p, int64_t ld, int64_t width, int elem) {
     return p == nullptr || (aligned(p, 16) && ld >= width && (ld * elem) % 16 == 0);
 }
 
-int drop_of(float p, uint64_t seed, uint64_t offset, Drop* d) {
+// where a launch takes its stream position from: immediates (cell == nullptr, dr false) or the device cell of the _dr entries, in
+// which case `offset` is the call's delta and `seed` is unused
+struct Rng {
+    bool dr;
+    uint64_t seed, offset;
+    const uint64_t* cell;
+};
+
+int drop_of(float p, const Rng& rng, Drop* d) {
     if (!(p >= 0.0f && p < 1.0f)) return DHAUG_EINVAL;                   // (a NaN fails the comparison)
-    d->seed = seed;
-    d->offset = offset;
+    if (rng.dr && p > 0.0f && rng.cell == nullptr) return DHAUG_EINVAL;  // (p == 0: the cell is not read and may be NULL)
+    if (rng.dr && p > 0.0f && (reinterpret_cast<uintptr_t>(rng.cell) & 7) != 0) return DHAUG_EALIGN;
+    d->seed = rng.seed;
+    d->offset = rng.offset;
     d->thresh = (unsigned)((double)p * 4294967296.0);
     d->inv_keep = 1.0f / (1.0f - p);
+    d->cell = reinterpret_cast<const unsigned long long*>(rng.cell);
     return DHAUG_OK;
 }
 
@@ -544,14 +573,25 @@ extern "C" int dhaug_bn_partials(const void* z, int z_bf16, int64_t ld_z, int64_
     return dhaug_launch_status();
 }
 
-extern "C" int dhaug_bn_act_forward(const void* z, int z_bf16, int64_t ld_z, const void* residual, int64_t ld_res,
-                                    const float* gamma, const float* beta, float* mean, float* rstd, const void* workspace,
-                                    float* running_mean, float* running_var, int64_t* num_batches_tracked, float momentum,
-                                    float eps, float p, uint64_t seed, uint64_t offset, uint16_t* y_bf16, int64_t ld_yb,
-                                    float* y_f32, int64_t ld_yf, int64_t M, int64_t C, void* stream) {
+namespace {
+
+template <typename T>
+void launch_forward(bool dr, dim3 grid, hipStream_t stream, const FwdArgs& a) {
+    if (dr)
+        hipLaunchKernelGGL((bn_act_forward_kernel<T, true>), grid, dim3(kBlock), 0, stream, a);
+    else
+        hipLaunchKernelGGL((bn_act_forward_kernel<T, false>), grid, dim3(kBlock), 0, stream, a);
+}
+
+// dhaug_bn_act_forward and dhaug_bn_act_forward_dr: one set of checks, one argument block
+int forward_launch(const void* z, int z_bf16, int64_t ld_z, const void* residual, int64_t ld_res, const float* gamma,
+                   const float* beta, float* mean, float* rstd, const void* workspace, float* running_mean, float* running_var,
+                   int64_t* num_batches_tracked, float momentum, float eps, float p, const Rng& rng, uint16_t* y_bf16, int64_t ld_yb,
+                   float* y_f32, int64_t ld_yf, int64_t M, int64_t C, void* stream) {
     FwdArgs a;
     DHAUG_CHECK(M >= 0 && C >= 0 && (z_bf16 == 0 || z_bf16 == 1), DHAUG_EINVAL);
-    DHAUG_CHECK(drop_of(p, seed, offset, &a.c.drop) == DHAUG_OK, DHAUG_EINVAL);
+    const int drc = drop_of(p, rng, &a.c.drop);
+    DHAUG_CHECK(drc == DHAUG_OK, drc);
     DHAUG_CHECK(eps >= 0.0f && momentum >= 0.0f && momentum <= 1.0f, DHAUG_EINVAL);
     if (M == 0 || C == 0) return DHAUG_OK;
     DHAUG_CHECK_PTR(z); DHAUG_CHECK_PTR(gamma); DHAUG_CHECK_PTR(beta); DHAUG_CHECK_PTR(mean); DHAUG_CHECK_PTR(rstd);
@@ -575,21 +615,44 @@ extern "C" int dhaug_bn_act_forward(const void* z, int z_bf16, int64_t ld_z, con
     a.momentum = momentum; a.eps = eps; a.yb = y_bf16; a.ld_yb = ld_yb; a.yf = y_f32; a.ld_yf = ld_yf;
     const dim3 grid(l.strips, l.chunks);
     if (z_bf16)
-        hipLaunchKernelGGL(bn_act_forward_kernel<uint16_t>, grid, dim3(kBlock), 0, (hipStream_t)stream, a);
+        launch_forward<uint16_t>(rng.dr, grid, (hipStream_t)stream, a);
     else
-        hipLaunchKernelGGL(bn_act_forward_kernel<float>, grid, dim3(kBlock), 0, (hipStream_t)stream, a);
+        launch_forward<float>(rng.dr, grid, (hipStream_t)stream, a);
     return dhaug_launch_status();
+}
+
+}  // namespace
+
+extern "C" int dhaug_bn_act_forward(const void* z, int z_bf16, int64_t ld_z, const void* residual, int64_t ld_res,
+                                    const float* gamma, const float* beta, float* mean, float* rstd, const void* workspace,
+                                    float* running_mean, float* running_var, int64_t* num_batches_tracked, float momentum,
+                                    float eps, float p, uint64_t seed, uint64_t offset, uint16_t* y_bf16, int64_t ld_yb,
+                                    float* y_f32, int64_t ld_yf, int64_t M, int64_t C, void* stream) {
+    return forward_launch(z, z_bf16, ld_z, residual, ld_res, gamma, beta, mean, rstd, workspace, running_mean, running_var,
+                          num_batches_tracked, momentum, eps, p, Rng{false, seed, offset, nullptr}, y_bf16, ld_yb, y_f32, ld_yf, M, C,
+                          stream);
+}
+
+extern "C" int dhaug_bn_act_forward_dr(const void* z, int z_bf16, int64_t ld_z, const void* residual, int64_t ld_res,
+                                       const float* gamma, const float* beta, float* mean, float* rstd, const void* workspace,
+                                       float* running_mean, float* running_var, int64_t* num_batches_tracked, float momentum,
+                                       float eps, float p, const uint64_t* rng_cell, uint64_t delta, uint16_t* y_bf16,
+                                       int64_t ld_yb, float* y_f32, int64_t ld_yf, int64_t M, int64_t C, void* stream) {
+    return forward_launch(z, z_bf16, ld_z, residual, ld_res, gamma, beta, mean, rstd, workspace, running_mean, running_var,
+                          num_batches_tracked, momentum, eps, p, Rng{true, 0, delta, rng_cell}, y_bf16, ld_yb, y_f32, ld_yf, M, C,
+                          stream);
 }
 
 namespace {
 
 // argument checks and the argument block shared by the two backward launches
 int backward_args(const void* z, int z_bf16, int64_t ld_z, const void* g, int64_t ld_g, const float* gamma, const float* beta,
-                  const float* mean, const float* rstd, float p, uint64_t seed, uint64_t offset, int64_t M, int64_t C,
-                  void* workspace, BwdArgs* a, Launch* l, bool* empty) {
+                  const float* mean, const float* rstd, float p, const Rng& rng, int64_t M, int64_t C, void* workspace, BwdArgs* a,
+                  Launch* l, bool* empty) {
     *empty = false;
     DHAUG_CHECK(M >= 0 && C >= 0 && (z_bf16 == 0 || z_bf16 == 1), DHAUG_EINVAL);
-    DHAUG_CHECK(drop_of(p, seed, offset, &a->c.drop) == DHAUG_OK, DHAUG_EINVAL);
+    const int drc = drop_of(p, rng, &a->c.drop);
+    DHAUG_CHECK(drc == DHAUG_OK, drc);
     if (M == 0 || C == 0) {
         *empty = true;
         return DHAUG_OK;
@@ -608,33 +671,46 @@ int backward_args(const void* z, int z_bf16, int64_t ld_z, const void* g, int64_
     return DHAUG_OK;
 }
 
-}  // namespace
+template <typename T>
+void launch_backward_partials(bool dr, dim3 grid, hipStream_t stream, const BwdArgs& a) {
+    if (dr)
+        hipLaunchKernelGGL((bn_act_backward_partials_kernel<T, true>), grid, dim3(kBlock), 0, stream, a);
+    else
+        hipLaunchKernelGGL((bn_act_backward_partials_kernel<T, false>), grid, dim3(kBlock), 0, stream, a);
+}
 
-extern "C" int dhaug_bn_act_backward_partials(const void* z, int z_bf16, int64_t ld_z, const void* g, int64_t ld_g,
-                                              const float* gamma, const float* beta, const float* mean, const float* rstd, float p,
-                                              uint64_t seed, uint64_t offset, int64_t M, int64_t C, void* workspace, void* stream) {
+template <typename T>
+void launch_backward(bool dr, dim3 grid, hipStream_t stream, const BwdArgs& a) {
+    if (dr)
+        hipLaunchKernelGGL((bn_act_backward_kernel<T, true>), grid, dim3(kBlock), 0, stream, a);
+    else
+        hipLaunchKernelGGL((bn_act_backward_kernel<T, false>), grid, dim3(kBlock), 0, stream, a);
+}
+
+int backward_partials_launch(const void* z, int z_bf16, int64_t ld_z, const void* g, int64_t ld_g, const float* gamma,
+                             const float* beta, const float* mean, const float* rstd, float p, const Rng& rng, int64_t M, int64_t C,
+                             void* workspace, void* stream) {
     BwdArgs a;
     Launch l;
     bool empty;
-    const int rc = backward_args(z, z_bf16, ld_z, g, ld_g, gamma, beta, mean, rstd, p, seed, offset, M, C, workspace, &a, &l, &empty);
+    const int rc = backward_args(z, z_bf16, ld_z, g, ld_g, gamma, beta, mean, rstd, p, rng, M, C, workspace, &a, &l, &empty);
     if (rc != DHAUG_OK || empty) return rc;
     const dim3 grid(l.strips, l.chunks);
     if (z_bf16)
-        hipLaunchKernelGGL(bn_act_backward_partials_kernel<uint16_t>, grid, dim3(kBlock), 0, (hipStream_t)stream, a);
+        launch_backward_partials<uint16_t>(rng.dr, grid, (hipStream_t)stream, a);
     else
-        hipLaunchKernelGGL(bn_act_backward_partials_kernel<float>, grid, dim3(kBlock), 0, (hipStream_t)stream, a);
+        launch_backward_partials<float>(rng.dr, grid, (hipStream_t)stream, a);
     return dhaug_launch_status();
 }
 
-extern "C" int dhaug_bn_act_backward(const void* z, int z_bf16, int64_t ld_z, const void* g, int64_t ld_g, const float* gamma,
-                                     const float* beta, const float* mean, const float* rstd, float p, uint64_t seed,
-                                     uint64_t offset, const void* workspace, uint16_t* dz_bf16, int64_t ld_dzb, float* dz_f32,
-                                     int64_t ld_dzf, float* dgamma, float* dbeta, int64_t M, int64_t C, void* stream) {
+int backward_launch(const void* z, int z_bf16, int64_t ld_z, const void* g, int64_t ld_g, const float* gamma, const float* beta,
+                    const float* mean, const float* rstd, float p, const Rng& rng, const void* workspace, uint16_t* dz_bf16,
+                    int64_t ld_dzb, float* dz_f32, int64_t ld_dzf, float* dgamma, float* dbeta, int64_t M, int64_t C, void* stream) {
     BwdArgs a;
     Launch l;
     bool empty;
-    const int rc = backward_args(z, z_bf16, ld_z, g, ld_g, gamma, beta, mean, rstd, p, seed, offset, M, C,
-                                 const_cast<void*>(workspace), &a, &l, &empty);
+    const int rc = backward_args(z, z_bf16, ld_z, g, ld_g, gamma, beta, mean, rstd, p, rng, M, C, const_cast<void*>(workspace), &a,
+                                 &l, &empty);
     if (rc != DHAUG_OK || empty) return rc;
     DHAUG_CHECK(dz_bf16 != nullptr || dz_f32 != nullptr, DHAUG_EINVAL);
     const int64_t Cp = (C + 15) / 16 * 16;
@@ -643,10 +719,43 @@ extern "C" int dhaug_bn_act_backward(const void* z, int z_bf16, int64_t ld_z, co
     a.dzb = dz_bf16; a.ld_dzb = ld_dzb; a.dzf = dz_f32; a.ld_dzf = ld_dzf; a.dgamma = dgamma; a.dbeta = dbeta;
     const dim3 grid(l.strips, l.chunks);
     if (z_bf16)
-        hipLaunchKernelGGL(bn_act_backward_kernel<uint16_t>, grid, dim3(kBlock), 0, (hipStream_t)stream, a);
+        launch_backward<uint16_t>(rng.dr, grid, (hipStream_t)stream, a);
     else
-        hipLaunchKernelGGL(bn_act_backward_kernel<float>, grid, dim3(kBlock), 0, (hipStream_t)stream, a);
+        launch_backward<float>(rng.dr, grid, (hipStream_t)stream, a);
     return dhaug_launch_status();
+}
+
+}  // namespace
+
+extern "C" int dhaug_bn_act_backward_partials(const void* z, int z_bf16, int64_t ld_z, const void* g, int64_t ld_g,
+                                              const float* gamma, const float* beta, const float* mean, const float* rstd, float p,
+                                              uint64_t seed, uint64_t offset, int64_t M, int64_t C, void* workspace, void* stream) {
+    return backward_partials_launch(z, z_bf16, ld_z, g, ld_g, gamma, beta, mean, rstd, p, Rng{false, seed, offset, nullptr}, M, C,
+                                    workspace, stream);
+}
+
+extern "C" int dhaug_bn_act_backward_partials_dr(const void* z, int z_bf16, int64_t ld_z, const void* g, int64_t ld_g,
+                                                 const float* gamma, const float* beta, const float* mean, const float* rstd,
+                                                 float p, const uint64_t* rng_cell, uint64_t delta, int64_t M, int64_t C,
+                                                 void* workspace, void* stream) {
+    return backward_partials_launch(z, z_bf16, ld_z, g, ld_g, gamma, beta, mean, rstd, p, Rng{true, 0, delta, rng_cell}, M, C,
+                                    workspace, stream);
+}
+
+extern "C" int dhaug_bn_act_backward(const void* z, int z_bf16, int64_t ld_z, const void* g, int64_t ld_g, const float* gamma,
+                                     const float* beta, const float* mean, const float* rstd, float p, uint64_t seed,
+                                     uint64_t offset, const void* workspace, uint16_t* dz_bf16, int64_t ld_dzb, float* dz_f32,
+                                     int64_t ld_dzf, float* dgamma, float* dbeta, int64_t M, int64_t C, void* stream) {
+    return backward_launch(z, z_bf16, ld_z, g, ld_g, gamma, beta, mean, rstd, p, Rng{false, seed, offset, nullptr}, workspace, dz_bf16,
+                           ld_dzb, dz_f32, ld_dzf, dgamma, dbeta, M, C, stream);
+}
+
+extern "C" int dhaug_bn_act_backward_dr(const void* z, int z_bf16, int64_t ld_z, const void* g, int64_t ld_g, const float* gamma,
+                                        const float* beta, const float* mean, const float* rstd, float p, const uint64_t* rng_cell,
+                                        uint64_t delta, const void* workspace, uint16_t* dz_bf16, int64_t ld_dzb, float* dz_f32,
+                                        int64_t ld_dzf, float* dgamma, float* dbeta, int64_t M, int64_t C, void* stream) {
+    return backward_launch(z, z_bf16, ld_z, g, ld_g, gamma, beta, mean, rstd, p, Rng{true, 0, delta, rng_cell}, workspace, dz_bf16,
+                           ld_dzb, dz_f32, ld_dzf, dgamma, dbeta, M, C, stream);
 }
 
 namespace {

@@ -24,6 +24,9 @@
 //  dhaug_adam_clip_step adam_dev_kernel's arithmetic (dhaug_elem.hip) with the clip coefficient.  Prologue: every workgroup adds the
 //                       partials in the same order (the launch-boundary reduce: no third launch), so all of them hold the same
 //                       norm and coef.  coef == 1 runs adam_dev_kernel's loop as it is written there: its bits.
+//  dhaug_adam_clip_step_lr  the same kernel instantiated with the learning rate read from one device float (a captured launch follows
+//                       the schedule); for an equal lr the same bits.
+//  dhaug_u64_add        *cell += value on a device uint64: the base of the posenet's device dropout stream, advanced once per step.
 // No atomics anywhere: the same call sequence gives the same bits.
 #include "dhaug_common.h"
 #include "dhaug_pose_regs.h"
@@ -239,12 +242,17 @@ __device__ __forceinline__ float clipped(float g, float gscale, float coef) {
     return gc;
 }
 
+// LR_DEV = false: lr is the launch's immediate.  LR_DEV = true (dhaug_adam_clip_step_lr): every workgroup reads the one device float
+// lr_dev, so a captured launch follows the schedule; everything after that load is the same statements.
+template <bool LR_DEV>
 __global__ __launch_bounds__(kBlock) void adam_clip_kernel(float* __restrict__ p, const float* __restrict__ g,
-                                                           float* __restrict__ m, float* __restrict__ v, long long n, float lr,
-                                                           float b1, float b2, float eps, const int* __restrict__ step_dev,
-                                                           float gscale, float max_norm, const double* __restrict__ partials,
-                                                           int nparts, float* __restrict__ norm_out, int vec) {
+                                                           float* __restrict__ m, float* __restrict__ v, long long n, float lr_imm,
+                                                           const float* __restrict__ lr_dev, float b1, float b2, float eps,
+                                                           const int* __restrict__ step_dev, float gscale, float max_norm,
+                                                           const double* __restrict__ partials, int nparts,
+                                                           float* __restrict__ norm_out, int vec) {
     __shared__ double lds[4];
+    const float lr = LR_DEV ? *lr_dev : lr_imm;
     double s = 0.0;
     for (int b = threadIdx.x; b < nparts; b += kBlock) s += partials[b];
     s = block_sum(s, lds);
@@ -372,19 +380,61 @@ extern "C" int dhaug_grad_sumsq(const float* grad, int64_t n, float grad_scale, 
     return dhaug_launch_status();
 }
 
-extern "C" int dhaug_adam_clip_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, float lr,
-                                    float beta1, float beta2, float eps, const int* step_dev, float grad_scale, float max_norm,
-                                    const void* workspace, float* norm_out, void* stream) {
+namespace {
+
+// dhaug_adam_clip_step and dhaug_adam_clip_step_lr: one set of checks, one launch shape
+int adam_clip_launch(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, float lr, const float* lr_dev,
+                     bool from_dev, float beta1, float beta2, float eps, const int* step_dev, float grad_scale, float max_norm,
+                     const void* workspace, float* norm_out, void* stream) {
     DHAUG_CHECK(n >= 0 && max_norm > 0.0f, DHAUG_EINVAL);                 // (a NaN max_norm fails the comparison)
     DHAUG_CHECK(step_dev != nullptr && workspace != nullptr, DHAUG_EINVAL);
+    DHAUG_CHECK(!from_dev || lr_dev != nullptr, DHAUG_EINVAL);
     if (n == 0) return DHAUG_OK;
     DHAUG_CHECK_PTR(param); DHAUG_CHECK_PTR(grad); DHAUG_CHECK_PTR(exp_avg); DHAUG_CHECK_PTR(exp_avg_sq);
     DHAUG_CHECK((reinterpret_cast<uintptr_t>(param) | reinterpret_cast<uintptr_t>(grad) | reinterpret_cast<uintptr_t>(exp_avg) |
                  reinterpret_cast<uintptr_t>(exp_avg_sq) | reinterpret_cast<uintptr_t>(step_dev) |
-                 reinterpret_cast<uintptr_t>(norm_out)) % 4 == 0 && reinterpret_cast<uintptr_t>(workspace) % 8 == 0, DHAUG_EALIGN);
+                 reinterpret_cast<uintptr_t>(norm_out) | reinterpret_cast<uintptr_t>(lr_dev)) % 4 == 0 &&
+                reinterpret_cast<uintptr_t>(workspace) % 8 == 0, DHAUG_EALIGN);
     const int vec = dhaug_aligned16(param) && dhaug_aligned16(grad) && dhaug_aligned16(exp_avg) && dhaug_aligned16(exp_avg_sq);
-    hipLaunchKernelGGL(adam_clip_kernel, dim3(dhaug_stream_grid((n + 3) / 4, kBlock, kMaxGrid)), dim3(kBlock), 0,
-                       (hipStream_t)stream, param, grad, exp_avg, exp_avg_sq, (long long)n, lr, beta1, beta2, eps, step_dev,
-                       grad_scale, max_norm, reinterpret_cast<const double*>(workspace), sumsq_grid(n), norm_out, vec);
+    const dim3 grid(dhaug_stream_grid((n + 3) / 4, kBlock, kMaxGrid));
+    if (from_dev)
+        hipLaunchKernelGGL(adam_clip_kernel<true>, grid, dim3(kBlock), 0, (hipStream_t)stream, param, grad, exp_avg, exp_avg_sq,
+                           (long long)n, 0.0f, lr_dev, beta1, beta2, eps, step_dev, grad_scale, max_norm,
+                           reinterpret_cast<const double*>(workspace), sumsq_grid(n), norm_out, vec);
+    else
+        hipLaunchKernelGGL(adam_clip_kernel<false>, grid, dim3(kBlock), 0, (hipStream_t)stream, param, grad, exp_avg, exp_avg_sq,
+                           (long long)n, lr, (const float*)nullptr, beta1, beta2, eps, step_dev, grad_scale, max_norm,
+                           reinterpret_cast<const double*>(workspace), sumsq_grid(n), norm_out, vec);
+    return dhaug_launch_status();
+}
+
+}  // namespace
+
+extern "C" int dhaug_adam_clip_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, float lr,
+                                    float beta1, float beta2, float eps, const int* step_dev, float grad_scale, float max_norm,
+                                    const void* workspace, float* norm_out, void* stream) {
+    return adam_clip_launch(param, grad, exp_avg, exp_avg_sq, n, lr, nullptr, false, beta1, beta2, eps, step_dev, grad_scale, max_norm,
+                            workspace, norm_out, stream);
+}
+
+extern "C" int dhaug_adam_clip_step_lr(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n,
+                                       const float* lr_dev, float beta1, float beta2, float eps, const int* step_dev,
+                                       float grad_scale, float max_norm, const void* workspace, float* norm_out, void* stream) {
+    return adam_clip_launch(param, grad, exp_avg, exp_avg_sq, n, 0.0f, lr_dev, true, beta1, beta2, eps, step_dev, grad_scale, max_norm,
+                            workspace, norm_out, stream);
+}
+
+namespace {
+
+// *cell += value on a 64-bit cell (the dropout stream's base): one workgroup, one thread, a plain load, add and vector store
+__global__ void u64_add_kernel(unsigned long long* cell, unsigned long long value) { *cell += value; }
+
+}  // namespace
+
+extern "C" int dhaug_u64_add(uint64_t* cell, uint64_t value, void* stream) {
+    DHAUG_CHECK_PTR(cell);
+    DHAUG_CHECK(reinterpret_cast<uintptr_t>(cell) % 8 == 0, DHAUG_EALIGN);
+    hipLaunchKernelGGL(u64_add_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, reinterpret_cast<unsigned long long*>(cell),
+                       (unsigned long long)value);
     return dhaug_launch_status();
 }

@@ -477,11 +477,11 @@ def video_mode_evaluate_posenet(args, data_dict, model_pos, model_pos_eval,
 def _video_train_epoch(fn, title, batches, model_pos, optimizer, criterion, device, args, single_frame_targets):
     """the epoch both video training loops share: per batch up to four steps in the reference's order -- plain, playback, flip,
     flip + playback (R/models_Fk_GAN/video_mode_operate.py:566-629, :686-749)"""
-    from ..function_aug.model_pos_train import StepRunner, set_grad, summary_line
+    from ..function_aug.model_pos_train import StepRunner, graph_requested, set_grad, summary_line
     torch.set_grad_enabled(True)
     set_grad([model_pos], True)
     model_pos.train()
-    run = StepRunner(model_pos, optimizer, criterion, device)
+    run = StepRunner(model_pos, optimizer, criterion, device, graph=graph_requested(args))
     flip, playback = bool(args.flip_pos_model_input), args.GAN_video_playback_input == True  # noqa: E712 (the reference's test)
     for b in batches(flip, playback):
         num_poses = b["inp"].shape[0]

@@ -23,10 +23,22 @@ def pattern_of(adj):
     return r.tolist(), c.tolist()
 
 
+_SCATTER_INDEX = {}
+
+
+def _scatter_index(rows, cols, joints, device):
+    """the pattern's flat positions as a device tensor, uploaded once per (pattern, device): an upload per call is a host
+    synchronisation, which a training step captured as a hipGraph may not contain"""
+    key = (tuple(rows), tuple(cols), joints, str(device))
+    if key not in _SCATTER_INDEX:
+        _SCATTER_INDEX[key] = torch.as_tensor([r * joints + c for r, c in zip(rows, cols)], dtype=torch.long, device=device)
+    return _SCATTER_INDEX[key]
+
+
 def softmax_adjacency(e, rows, cols, joints):
     """e (L, nnz) -> (L, J, J): one scatter and one softmax for L layers"""
     flat = e.new_full((e.shape[0], joints * joints), NEG)
-    idx = torch.as_tensor([r * joints + c for r, c in zip(rows, cols)], dtype=torch.long, device=e.device)
+    idx = _scatter_index(rows, cols, joints, e.device)
     return torch.softmax(flat.index_copy(1, idx, e).view(-1, joints, joints), dim=2)
 
 

@@ -487,10 +487,22 @@ def grad_sumsq(grad, grad_scale=1.0, workspace=None, step_counter=None):
     return ws
 
 
+def u64_add(cell, value):
+    """*cell += value on one element of an int64 device tensor read as uint64 (dhaug_u64_add, one launch in stream order)"""
+    if not cell.is_cuda:
+        raise RuntimeError("dhaug op `u64_add` needs a GPU tensor (no CPU fallback exists)")
+    if cell.dtype != torch.int64 or cell.numel() != 1:
+        raise ValueError("u64_add: cell must be one int64 element, got %s %s" % (cell.dtype, tuple(cell.shape)))
+    _lib.call("dhaug_u64_add", _p(cell), int(value) & 0xFFFFFFFFFFFFFFFF, _stream())
+    return cell
+
+
 def adam_clip_step(param, grad, exp_avg, exp_avg_sq, step_dev, workspace, max_norm, lr=1e-3, betas=(0.9, 0.999), eps=1e-8,
                    grad_scale=1.0, norm_out=None):
     """clip_grad_norm_(max_norm) + Adam.step() from the partials of grad_sumsq(grad, grad_scale, workspace) (dhaug_adam_clip_step);
-    *step_dev is the step count (already advanced).  Returns the gradient norm as a 1-element fp32 device tensor."""
+    *step_dev is the step count (already advanced).  lr: a number, or a 1-element fp32 device tensor that the launch reads when it
+    runs (dhaug_adam_clip_step_lr: a captured launch follows the schedule).  Returns the gradient norm as a 1-element fp32 device
+    tensor."""
     n = param.numel()
     vectors = ((param, "param"), (grad, "grad"), (exp_avg, "exp_avg"), (exp_avg_sq, "exp_avg_sq"))
     for t, what in vectors:
@@ -504,6 +516,12 @@ def adam_clip_step(param, grad, exp_avg, exp_avg_sq, step_dev, workspace, max_no
     assert step_dev.dtype == torch.int32
     if norm_out is None:
         norm_out = torch.empty(1, dtype=torch.float32, device=param.device)
+    if torch.is_tensor(lr):
+        if not (lr.is_cuda and lr.dtype == torch.float32 and lr.numel() == 1):
+            raise ValueError("adam_clip_step: a tensor lr must be one fp32 device element, got %s %s" % (lr.dtype, tuple(lr.shape)))
+        _lib.call("dhaug_adam_clip_step_lr", _p(param), _p(grad), _p(exp_avg), _p(exp_avg_sq), n, _p(lr), betas[0], betas[1], eps,
+                  _p(step_dev), float(grad_scale), max_norm, _p(workspace), _p(norm_out), _stream())
+        return norm_out
     _lib.call("dhaug_adam_clip_step", _p(param), _p(grad), _p(exp_avg), _p(exp_avg_sq), n, float(lr), betas[0], betas[1], eps,
               _p(step_dev), float(grad_scale), max_norm, _p(workspace), _p(norm_out), _stream())
     return norm_out
@@ -924,6 +942,14 @@ def gemm_tn_group(items, max_workgroups=0):
         _lib.call("dhaug_gemm_tn_group_bf16", arr, len(chunk), _p(_tn_group_workspace(chunk[0].A.device)), _stream())
 
 
+# Set while the posenet step is captured (function_aug.model_pos_train.StepRunner): gemm_tn and colsum then zero a fresh output with a
+# fill KERNEL and call the library in its accumulating form, instead of letting it issue hipMemset2DAsync / hipMemsetAsync.  Measured
+# on an MI355X: the memset nodes of the most recently captured step stopped zeroing once the allocator had released cached memory
+# (torch.cuda.empty_cache, which every later capture calls) -- the replayed weight gradient then came out as 1e23 .. 1e30, while the
+# same step with kernel nodes only replays the eager path's bits.  The sums are the same either way (zero, then atomic adds).
+ZERO_BY_KERNEL = False
+
+
 def gemm_tn(A, B, N1, N2, out=None, accumulate=False, M=None, lda=None, ldb=None, colsum=None, colsum_rows=None):
     """C[N1,N2] (+)= A[M,N1]^T B[M,N2], bf16 operands, fp32 result; colsum (fp32 [N1], optional) (+)= column sums of A
     (over rows [0, colsum_rows) only when given: a multiple of 128)."""
@@ -938,6 +964,11 @@ def gemm_tn(A, B, N1, N2, out=None, accumulate=False, M=None, lda=None, ldb=None
         # a long 256 x 256 contraction alone: a group of one (whole-output tiles, dhaug_tn256.hip)
         gemm_tn_group([TnItem(A=A, B=B, N1=N1, N2=N2, out=out, colsum=colsum, colsum_rows=cr, accumulate=accumulate, M=M, lda=la, ldb=lb)])
         return out
+    if ZERO_BY_KERNEL and not accumulate:
+        out.zero_()
+        if colsum is not None:
+            colsum.zero_()
+        accumulate = True
     _lib.call("dhaug_gemm_tn_bf16_rows", _p(A), la, _p(B), lb, _p(out), out.stride(0), _p(colsum), cr, M, N1, N2, int(accumulate), _stream())
     return out
 
@@ -948,6 +979,9 @@ def colsum(src, N=None, out=None, accumulate=False):
         out = torch.empty((N,), dtype=torch.float32, device=src.device)
         accumulate = False
     name = "dhaug_colsum_bf16" if src.dtype == BF16 else "dhaug_colsum_f32"
+    if ZERO_BY_KERNEL and not accumulate:
+        out.zero_()
+        accumulate = True
     _lib.call(name, _p(src), src.stride(0), _p(out), src.shape[0], N, int(accumulate), _stream())
     return out
 
@@ -1204,12 +1238,24 @@ def _bn_outputs(M, C, dev, out_bf16, out_f32):
     return yb, yf
 
 
+def _bn_rng(rng, name):
+    """(entry suffix, the two rng arguments): rng = (seed, offset) as numbers, or (cell, delta) with cell a 2-element int64 device
+    tensor {seed, base} that the launch reads when it runs (the _dr entries)"""
+    if torch.is_tensor(rng[0]):
+        cell = rng[0]
+        if not (cell.is_cuda and cell.dtype == torch.int64 and cell.numel() == 2 and cell.is_contiguous()):
+            raise ValueError("%s: an rng cell must be a contiguous int64 device tensor of 2 elements {seed, base}" % name)
+        return "_dr", (_p(cell), int(rng[1]) & 0xFFFFFFFFFFFFFFFF)
+    return "", (int(rng[0]), int(rng[1]))
+
+
 def bn_act_forward(z, C, gamma, beta, residual=None, stats=None, buffers=None, momentum=0.1, eps=1e-5, p=0.0, rng=(0, 0),
                    workspace=None, out_bf16=None, out_f32=None):
     """y = dropout_p(relu(batchnorm(z))) (+ residual) over the first C columns of z (M, >= C; fp32 or bf16; residual of the same type),
     dhaug_bn_partials + dhaug_bn_act_forward.  stats = (mean, rstd): the given-statistics mode (one launch, nothing updated);
     otherwise batch statistics, and buffers = (running_mean, running_var, num_batches_tracked) are updated as nn.BatchNorm1d does.
-    rng = (seed, offset) of the dropout's Philox stream.  Returns (y_bf16 (M, ceil16 C) | None, y_f32 (M, C) | None, mean, rstd);
+    rng = (seed, offset) of the dropout's Philox stream, or (cell, delta): seed = cell[0], offset = cell[1] + delta, read on the
+    device (dhaug_bn_act_forward_dr).  Returns (y_bf16 (M, ceil16 C) | None, y_f32 (M, C) | None, mean, rstd);
     by default the output has z's type."""
     z, ld_z = _bn_rows(z, C, "bn_act_forward", "z")
     M, dev, zb = z.shape[0], z.device, z.dtype == BF16
@@ -1232,15 +1278,16 @@ def bn_act_forward(z, C, gamma, beta, residual=None, stats=None, buffers=None, m
             _bn_vec(rm, C, "bn_act_forward", "running_mean"), _bn_vec(rv, C, "bn_act_forward", "running_var")
             assert nbt is None or (nbt.is_cuda and nbt.dtype == torch.int64 and nbt.numel() == 1)
         _lib.call("dhaug_bn_partials", _p(z), int(zb), ld_z, M, C, _p(ws), _stream())
-    _lib.call("dhaug_bn_act_forward", _p(z), int(zb), ld_z, _p(res), ld_res, _p(g), _p(b), _p(mean), _p(rstd), _p(ws), _p(rm), _p(rv),
-              _p(nbt), float(momentum), float(eps), float(p), int(rng[0]), int(rng[1]), _p(yb), 0 if yb is None else yb.stride(0),
+    dr, rng_args = _bn_rng(rng, "bn_act_forward")
+    _lib.call("dhaug_bn_act_forward" + dr, _p(z), int(zb), ld_z, _p(res), ld_res, _p(g), _p(b), _p(mean), _p(rstd), _p(ws), _p(rm), _p(rv),
+              _p(nbt), float(momentum), float(eps), float(p), rng_args[0], rng_args[1], _p(yb), 0 if yb is None else yb.stride(0),
               _p(yf), 0 if yf is None else yf.stride(0), M, C, _stream())
     return yb, yf, mean, rstd
 
 
 def bn_act_backward(z, C, g, gamma, beta, mean, rstd, p=0.0, rng=(0, 0), workspace=None, out_bf16=None, out_f32=None):
     """backward of bn_act_forward's branch for the cotangent g (z's type and rows): (dz_bf16 | None, dz_f32 | None, dgamma, dbeta);
-    dhaug_bn_act_backward_partials + dhaug_bn_act_backward with the forward call's (p, rng)."""
+    dhaug_bn_act_backward_partials + dhaug_bn_act_backward (their _dr forms for rng = (cell, delta)) with the forward call's (p, rng)."""
     z, ld_z = _bn_rows(z, C, "bn_act_backward", "z")
     g, ld_g = _bn_rows(g, C, "bn_act_backward", "g", z)
     M, dev, zb = z.shape[0], z.device, z.dtype == BF16
@@ -1251,9 +1298,10 @@ def bn_act_backward(z, C, g, gamma, beta, mean, rstd, p=0.0, rng=(0, 0), workspa
     dgamma, dbeta = torch.empty(C, dtype=torch.float32, device=dev), torch.empty(C, dtype=torch.float32, device=dev)
     ws = workspace if workspace is not None else bn_workspace(C, dev)
     assert ws.is_cuda and ws.dtype == torch.float64 and ws.numel() >= _lib.BN_MAX_CHUNKS * 2 * C
-    head = (_p(z), int(zb), ld_z, _p(g), ld_g, _p(vec[0]), _p(vec[1]), _p(vec[2]), _p(vec[3]), float(p), int(rng[0]), int(rng[1]))
-    _lib.call("dhaug_bn_act_backward_partials", *head, M, C, _p(ws), _stream())
-    _lib.call("dhaug_bn_act_backward", *head, _p(ws), _p(dzb), 0 if dzb is None else dzb.stride(0), _p(dzf),
+    dr, rng_args = _bn_rng(rng, "bn_act_backward")
+    head = (_p(z), int(zb), ld_z, _p(g), ld_g, _p(vec[0]), _p(vec[1]), _p(vec[2]), _p(vec[3]), float(p)) + rng_args
+    _lib.call("dhaug_bn_act_backward_partials" + dr, *head, M, C, _p(ws), _stream())
+    _lib.call("dhaug_bn_act_backward" + dr, *head, _p(ws), _p(dzb), 0 if dzb is None else dzb.stride(0), _p(dzf),
               0 if dzf is None else dzf.stride(0), _p(dgamma), _p(dbeta), M, C, _stream())
     return dzb, dzf, dgamma, dbeta
 

@@ -304,10 +304,20 @@ class PosenetAdam(FusedAdam):
         if dst:
             torch._foreach_copy_(dst, src)
 
+    def note_step(self):
+        """the host bookkeeping of one clip_step and nothing else: a replayed hipGraph of the step has done the device's part
+        (the parameters, the moments, step_dev), so the packed copies cached on the parameters are stale, the host's count
+        advances, and torch's lr schedulers see that a step preceded scheduler.step()"""
+        self._stale_packs()
+        self.step_count += 1
+        self._opt_called = True
+
     @torch.no_grad()
-    def clip_step(self, max_norm, norm_out=None):
+    def clip_step(self, max_norm, norm_out=None, lr_dev=None):
         """nn.utils.clip_grad_norm_(parameters, max_norm) followed by step(): the exchange (all-reduce sum when distributed, the
         kernels scale by 1 / world, so the norm is that of the AVERAGED gradient), dhaug_grad_sumsq, dhaug_adam_clip_step.
+        lr_dev: a 1-element fp32 device tensor holding the learning rate, read by the launch when it runs
+        (dhaug_adam_clip_step_lr) in place of param_groups[0]['lr'] -- what a captured step needs under a schedule.
         Returns the norm as a 1-element fp32 device tensor (norm_out if given); nothing is read on the host."""
         if not self.flat_param.is_cuda:
             raise RuntimeError("PosenetAdam needs GPU parameters (no CPU fallback exists)")
@@ -317,12 +327,10 @@ class PosenetAdam(FusedAdam):
         self._check_views()
         self.flush()
         ws = self.exchange()
-        self.step_count += 1
-        self._opt_called = True                 # what torch's lr schedulers look at to see that a step preceded scheduler.step()
         if self._workspace is None:
             self._workspace = ops.posetrain_workspace(self.flat_param.device)
         g = self.param_groups[0]
-        self._stale_packs()
+        self.note_step()
         ops.grad_sumsq(self.flat_grad, 1.0 / ws, self._workspace, self.step_dev)
         return ops.adam_clip_step(self.flat_param, self.flat_grad, self.exp_avg, self.exp_avg_sq, self.step_dev, self._workspace,
-                                  max_norm, g["lr"], tuple(g["betas"]), g["eps"], 1.0 / ws, norm_out)
+                                  max_norm, g["lr"] if lr_dev is None else lr_dev, tuple(g["betas"]), g["eps"], 1.0 / ws, norm_out)

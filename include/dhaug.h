@@ -326,6 +326,16 @@ int dhaug_grad_sumsq(const float* grad, int64_t n, float grad_scale, void* works
 int dhaug_adam_clip_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, float lr, float beta1,
                          float beta2, float eps, const int* step_dev, float grad_scale, float max_norm, const void* workspace,
                          float* norm_out, void* stream);
+/* dhaug_adam_clip_step_lr: dhaug_adam_clip_step with the learning rate in device memory, for a launch that is captured once and
+ *   replayed under a schedule.  lr_dev: one device float (4-byte aligned), read by every workgroup; every other argument, check and
+ *   code is dhaug_adam_clip_step's, and for *lr_dev == lr the parameters, both moments and norm_out are its bits (one kernel,
+ *   instantiated for the two sources of lr).  DHAUG_EINVAL in addition: NULL lr_dev (checked before n = 0 returns). */
+int dhaug_adam_clip_step_lr(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, const float* lr_dev,
+                            float beta1, float beta2, float eps, const int* step_dev, float grad_scale, float max_norm,
+                            const void* workspace, float* norm_out, void* stream);
+/* *cell += value on a device uint64 (8-byte aligned: DHAUG_EALIGN otherwise; NULL: DHAUG_EINVAL), a one-workgroup launch in stream
+ *   order like dhaug_counter_add: the base of the device dropout stream (dhaug_bn_act_forward_dr) is advanced with it once per step. */
+int dhaug_u64_add(uint64_t* cell, uint64_t value, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------
  * Dense layers: bf16 MFMA GEMM with fused epilogue
@@ -943,6 +953,24 @@ int dhaug_bn_act_backward(const void* z, int z_bf16, int64_t ld_z, const void* g
                           const float* beta, const float* mean, const float* rstd, float p, uint64_t seed, uint64_t offset,
                           const void* workspace, uint16_t* dz_bf16, int64_t ld_dzb, float* dz_f32, int64_t ld_dzf, float* dgamma,
                           float* dbeta, int64_t M, int64_t C, void* stream);
+/* The device-stream forms of the three launches above (dhaug_bn_act_forward, dhaug_bn_act_backward_partials, dhaug_bn_act_backward):
+ * the same kernels instantiated a second time, with (seed, offset) replaced by (rng_cell, delta).  rng_cell: two device uint64
+ * {seed, base}, 8-byte aligned (DHAUG_EALIGN otherwise); the launch uses seed = rng_cell[0] and offset = rng_cell[1] + delta, a full
+ * 64-bit sum, read when it runs -- so a captured launch draws a new mask at every replay once the base has been advanced
+ * (dhaug_u64_add).  For equal (seed, offset) every output is bit-identical to the entry it mirrors.  p = 0: the cell is not read and
+ * may be NULL; p > 0 with a NULL cell: DHAUG_EINVAL before any launch.  Every other argument, check and code is the mirrored entry's. */
+int dhaug_bn_act_forward_dr(const void* z, int z_bf16, int64_t ld_z, const void* residual, int64_t ld_res, const float* gamma,
+                            const float* beta, float* mean, float* rstd, const void* workspace, float* running_mean,
+                            float* running_var, int64_t* num_batches_tracked, float momentum, float eps, float p,
+                            const uint64_t* rng_cell, uint64_t delta, uint16_t* y_bf16, int64_t ld_yb, float* y_f32, int64_t ld_yf,
+                            int64_t M, int64_t C, void* stream);
+int dhaug_bn_act_backward_partials_dr(const void* z, int z_bf16, int64_t ld_z, const void* g, int64_t ld_g, const float* gamma,
+                                      const float* beta, const float* mean, const float* rstd, float p, const uint64_t* rng_cell,
+                                      uint64_t delta, int64_t M, int64_t C, void* workspace, void* stream);
+int dhaug_bn_act_backward_dr(const void* z, int z_bf16, int64_t ld_z, const void* g, int64_t ld_g, const float* gamma,
+                             const float* beta, const float* mean, const float* rstd, float p, const uint64_t* rng_cell,
+                             uint64_t delta, const void* workspace, uint16_t* dz_bf16, int64_t ld_dzb, float* dz_f32, int64_t ld_dzf,
+                             float* dgamma, float* dbeta, int64_t M, int64_t C, void* stream);
 int dhaug_bn_fold(const float* W, int64_t ldw, const float* gamma, const float* beta, const float* running_mean,
                   const float* running_var, float eps, float* W_out, int64_t ld_out, float* bias_out, float* rstd_out, int64_t N,
                   int64_t K, void* stream);

@@ -8,7 +8,10 @@ All variants in ONE process, warmed up, then alternating: five rounds, every var
 forwards under no_grad) per round between HIP events on the stream; the median of a variant's five rounds is reported, with the
 rounds behind it.  No speed is promised: the network has 0.27 M parameters and its step is a chain of small launches.
 
-    python tools/time_gcn.py [--steps 50]"""
+--graph: the training step alone, with a third line per precision: "<precision>+graph" = StepRunner(graph=True), the step replayed as a
+hipGraph, beside the launch-by-launch step and the stock module.
+
+    python tools/time_gcn.py [--steps 50] [--graph]"""
 import argparse
 import os
 import sys
@@ -27,6 +30,7 @@ import gcn_util as CU
 
 B, HID, BLOCKS, DROPOUT = 1024, 128, 4, 0.25
 VARIANTS = ("stock", "bf16", "bf16x3", "bf16x6")
+GRAPH_VARIANTS = ("stock",) + tuple(v + s for v in VARIANTS[1:] for s in ("", "+graph"))
 
 
 def build(variant):
@@ -43,8 +47,11 @@ def runners(variant, steps):
     g = torch.Generator(device="cuda").manual_seed(1)
     x = torch.randn(B, 16, 2, device="cuda", generator=g) * 0.4
     t = torch.randn(B, 16, 3, device="cuda", generator=g) * 0.3
+    variant, _, graph = variant.partition("+")
     model = build(variant)
-    run = T.StepRunner(model, T.posenet_optimizer(model, 1e-4), nn.MSELoss(reduction="mean"), torch.device("cuda"))
+    if graph:
+        model.train()
+    run = T.StepRunner(model, T.posenet_optimizer(model, 1e-4), nn.MSELoss(reduction="mean"), torch.device("cuda"), graph=bool(graph))
 
     def train():
         model.train()
@@ -74,21 +81,25 @@ def timed(fn):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=50)
+    ap.add_argument("--graph", action="store_true")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("tools/time_gcn.py needs a GPU: a time taken anywhere else says nothing")
-    runs = {v: runners(v, a.steps) for v in VARIANTS}
+    variants = GRAPH_VARIANTS if a.graph else VARIANTS
+    runs = {v: runners(v, a.steps) for v in variants}
     for train, evaluate in runs.values():                           # warm-up: every shape the timed windows use
         train(), evaluate()
-    ts = {(v, k): [] for v in VARIANTS for k in ("train", "eval")}
+    ts = {(v, k): [] for v in variants for k in ("train", "eval")}
     for _ in range(5):
         for v, (train, evaluate) in runs.items():
             ts[(v, "train")].append(timed(train) / a.steps)
-            ts[(v, "eval")].append(timed(evaluate) / a.steps)
-    for k, what in (("train", "training step (forward, loss, backward, clip + Adam)"), ("eval", "evaluation forward")):
-        for v in VARIANTS:
+            if not a.graph:
+                ts[(v, "eval")].append(timed(evaluate) / a.steps)
+    sides = (("train", "training step (forward, loss, backward, clip + Adam)"), ("eval", "evaluation forward"))
+    for k, what in sides[:1 if a.graph else 2]:
+        for v in variants:
             r = ts[(v, k)]
-            print("gcn=%-6s: %.3f ms per %s at B = %d (median of 5 alternating rounds of %d; rounds %s)"
+            print("gcn=%-12s: %.3f ms per %s at B = %d (median of 5 alternating rounds of %d; rounds %s)"
                   % (v, float(np.median(r)), what, B, a.steps, " ".join("%.3f" % q for q in r)), flush=True)
 
 

@@ -8,7 +8,10 @@ restatement (tests/linear_model_util.StockMLP: nn.Linear / nn.BatchNorm1d / nn.D
 All variants of a side run in ONE process, warmed up, then alternating: five rounds of 50 calls per variant between HIP events; the
 median of a variant's five rounds is reported.  Reported, not gated.
 
-    python tools/time_linear_model.py [--calls 50]"""
+--graph: the training side alone, with a third line per precision: "<precision>+graph" = StepRunner(graph=True), the step replayed as a
+hipGraph, beside the launch-by-launch step and the stock module.
+
+    python tools/time_linear_model.py [--calls 50] [--graph]"""
 import argparse
 import os
 import sys
@@ -27,6 +30,7 @@ import linear_model_util as LU
 
 B, C, DROPOUT = 1024, 1024, 0.25
 VARIANTS = ("stock", "bf16", "bf16x3", "bf16x6")
+GRAPH_VARIANTS = ("stock",) + tuple(v + s for v in VARIANTS[1:] for s in ("", "+graph"))
 
 
 def build(variant, stages):
@@ -39,9 +43,10 @@ def build(variant, stages):
 
 
 def train_fn(variant, stages, x, t):
+    variant, _, graph = variant.partition("+")
     model = build(variant, stages).train()
     opt = torch.optim.Adam(model.parameters(), lr=1e-4) if variant == "stock" else T.posenet_optimizer(model, 1e-4)
-    run = T.StepRunner(model, opt, nn.MSELoss(reduction="mean"), torch.device("cuda"))
+    run = T.StepRunner(model, opt, nn.MSELoss(reduction="mean"), torch.device("cuda"), graph=bool(graph))
 
     return lambda: run.step(x, t, "loss", B)
 
@@ -76,18 +81,20 @@ def measure(fns, calls):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--calls", type=int, default=50)
+    ap.add_argument("--graph", action="store_true")
     a = ap.parse_args()
     g = torch.Generator(device="cuda").manual_seed(1)
     x = torch.randn(B, 16, 2, device="cuda", generator=g) * 0.4
     t = torch.randn(B, 16, 3, device="cuda", generator=g) * 0.3
     t[:, 0] = 0
     for stages in (2, 4):
-        for side, make in (("training step", train_fn), ("evaluation forward", eval_fn)):
-            ts = measure({v: make(v, stages, x, t) for v in VARIANTS}, a.calls)
+        for side, make in (("training step", train_fn), ("evaluation forward", eval_fn))[:1 if a.graph else 2]:
+            variants = GRAPH_VARIANTS if a.graph else VARIANTS
+            ts = measure({v: make(v, stages, x, t) for v in variants}, a.calls)
             stock = float(np.median(ts["stock"]))
-            for v in VARIANTS:
+            for v in variants:
                 med = float(np.median(ts[v]))
-                print("mlp stages=%d %-18s %-6s: %8.1f us (%.2f x stock; median of 5 alternating rounds of %d; rounds %s)"
+                print("mlp stages=%d %-18s %-12s: %8.1f us (%.2f x stock; median of 5 alternating rounds of %d; rounds %s)"
                       % (stages, side, v, med, med / stock, a.calls, " ".join("%.1f" % r for r in ts[v])), flush=True)
 
 

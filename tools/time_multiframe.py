@@ -13,7 +13,10 @@ Evaluation: multiFrame_TemporalModel on one sequence of 2 000 frames (gradients 
 All variants of a workload run in ONE process, warmed up, then alternating: --rounds rounds (at least five), each variant --steps steps
 per round between HIP events; the median of a variant's rounds is reported.
 
-    python tools/time_multiframe.py [--steps 20] [--rounds 5] [--arch 3,3 --arch 3,3,3]"""
+--graph: the training side alone, variants "<precision>", "<precision>+graph" (StepRunner(graph=True): the step replayed as a hipGraph)
+and the stock module.
+
+    python tools/time_multiframe.py [--steps 20] [--rounds 5] [--arch 3,3 --arch 3,3,3] [--graph]"""
 import argparse
 import contextlib
 import os
@@ -35,6 +38,7 @@ import multiframe_util as MU
 B, C, EVAL_FRAMES = 512, 1024, 2000
 TRAIN_VARIANTS = ("bf16", "bf16x6", "stock", "bf16-permute", "bf16x6-permute")
 EVAL_VARIANTS = ("bf16", "bf16x6", "stock")
+GRAPH_VARIANTS = ("bf16", "bf16+graph", "bf16x6", "bf16x6+graph", "stock")
 
 
 @contextlib.contextmanager
@@ -65,13 +69,15 @@ def train_fn(variant, arch, steps):
     x = torch.randn(B, rf, 16, 2, device="cuda", generator=g) * 0.4
     t = torch.randn(B, 1, 16, 3, device="cuda", generator=g) * 0.3
     torch.manual_seed(0)
+    variant, _, graph = variant.partition("+")
     if variant == "stock":
         model = MU.StockMultiFrame(C, arch, True, dropout=0.25).cuda()
     else:
         model = multiFrame_TemporalModelOptimized1f(16, 2, 16, filter_widths=list(arch), dropout=0.25, channels=C).cuda()
         model.precision = variant.split("-")[0]
     model.train()
-    runner = T.StepRunner(model, T.posenet_optimizer(model, 1e-4), nn.MSELoss(reduction="mean"), torch.device("cuda"))
+    runner = T.StepRunner(model, T.posenet_optimizer(model, 1e-4), nn.MSELoss(reduction="mean"), torch.device("cuda"),
+                          graph=bool(graph))
     ctx = torch_permute if variant.endswith("-permute") else contextlib.nullcontext
 
     def run():
@@ -124,12 +130,15 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--arch", action="append")
+    ap.add_argument("--graph", action="store_true")
     a = ap.parse_args()
     if a.rounds < 5:
         ap.error("--rounds must be at least 5 (the median of fewer blocks is not reported)")
     for arch in (a.arch or ["3,3", "3,3,3"]):
         arch = tuple(int(w) for w in arch.split(","))
-        measure("train step B=%d" % B, TRAIN_VARIANTS, train_fn, arch, a.steps, a.rounds)
+        measure("train step B=%d" % B, GRAPH_VARIANTS if a.graph else TRAIN_VARIANTS, train_fn, arch, a.steps, a.rounds)
+        if a.graph:
+            continue
         measure("eval %d frames" % EVAL_FRAMES, EVAL_VARIANTS, eval_fn, arch, a.steps, a.rounds)
 
 

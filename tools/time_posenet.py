@@ -9,7 +9,10 @@ models_baseline.videopose.TemporalModelOptimized1f in each precision ("bf16", "b
   (b) launches per optimizer step: a rocprofv3 --kernel-trace --stats run of this file (--part k) per variant at two epoch lengths
       in child processes; (calls(N2) - calls(N1)) / (2 (N2 - N1)) leaves the start-up launches out
 
-    python tools/time_posenet.py [--batches 50] [--no-launches]"""
+  --graph: part (a) alone, with a third line per precision: "<precision>+graph" = the same loop with args.posenet_graph (the step
+      replayed as a hipGraph, function_aug.model_pos_train.StepRunner(graph=True)) beside the launch-by-launch loop and the stock module
+
+    python tools/time_posenet.py [--batches 50] [--no-launches] [--graph]"""
 import argparse
 import csv
 import glob
@@ -35,6 +38,7 @@ from time_posetrain import WideMLP
 
 B = 1024
 VARIANTS = ("stock", "bf16", "bf16x3", "bf16x6")
+GRAPH_VARIANTS = ("stock",) + tuple(v + s for v in VARIANTS[1:] for s in ("", "+graph"))
 
 
 def epoch_fn(variant, nb):
@@ -42,6 +46,7 @@ def epoch_fn(variant, nb):
     t3 = torch.randn(nb * B, 16, 3, device="cuda", generator=g)
     i2 = torch.randn(nb * B, 16, 2, device="cuda", generator=g) * 0.4
     torch.manual_seed(0)
+    variant, _, graph = variant.partition("+")
     if variant == "stock":
         model = WideMLP().cuda()
     else:
@@ -49,14 +54,15 @@ def epoch_fn(variant, nb):
         model.precision = variant
     opt = T.posenet_optimizer(model, 1e-4)
     loader, crit, args, device = TensorLoader([t3, i2], B), nn.MSELoss(reduction="mean"), PU.loop_args(), torch.device("cuda")
+    args.posenet_graph = bool(graph)
     return lambda: T.train_posenet(model, loader, opt, crit, device, args)
 
 
-def part_a(nb):
-    runs = {v: epoch_fn(v, nb) for v in VARIANTS}
+def part_a(nb, variants=VARIANTS):
+    runs = {v: epoch_fn(v, nb) for v in variants}
     for run in runs.values():
-        run()                                                     # warm-up: 2 nb steps each
-    ts = {v: [] for v in VARIANTS}
+        run()                                                     # warm-up: 2 nb steps each (a graph variant captures its two steps here)
+    ts = {v: [] for v in variants}
     for _ in range(5):
         for v, run in runs.items():
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -66,8 +72,8 @@ def part_a(nb):
             e1.record()
             e1.synchronize()
             ts[v].append(e0.elapsed_time(e1) / nb)
-    for v in VARIANTS:
-        print("posenet=%-6s: %.3f ms per batch of %d = plain + flipped step (median of 5 alternating epochs of %d steps; epochs %s)"
+    for v in variants:
+        print("posenet=%-12s: %.3f ms per batch of %d = plain + flipped step (median of 5 alternating epochs of %d steps; epochs %s)"
               % (v, float(np.median(ts[v])), B, 2 * nb, " ".join("%.3f" % t for t in ts[v])), flush=True)
 
 
@@ -92,14 +98,15 @@ def main():
     ap.add_argument("--variant", default="stock")
     ap.add_argument("--batches", type=int, default=50)
     ap.add_argument("--no-launches", action="store_true")
+    ap.add_argument("--graph", action="store_true")
     a = ap.parse_args()
     T.summary_line = lambda *x, **k: None                        # one line per epoch would drown the report
     if a.part == "k":
         epoch_fn(a.variant, a.batches)()
         torch.cuda.synchronize()
         return
-    part_a(a.batches)
-    if not a.no_launches:
+    part_a(a.batches, GRAPH_VARIANTS if a.graph else VARIANTS)
+    if not a.no_launches and not a.graph:
         n1, n2 = 4, 12
         for v in VARIANTS:
             c1, c2 = kernel_calls(v, n1), kernel_calls(v, n2)
