@@ -116,6 +116,8 @@ ATTN_MAX_TOKENS = 81                                   # DHAUG_ATTN_MAX_TOKENS
 ATTN_MAX_HEAD_DIM = 64                                 # DHAUG_ATTN_MAX_HEAD_DIM
 ATTN_MAX_BLOCKS = 8192                                 # DHAUG_ATTN_MAX_BLOCKS
 GELU_MAX_BLOCKS = 2048                                 # DHAUG_GELU_MAX_BLOCKS
+FK_MAX_BLOCKS = 10240                                  # DHAUG_FK_MAX_BLOCKS
+GEN_TAIL4_MAX_BLOCKS = 4096                            # DHAUG_GEN_TAIL4_MAX_BLOCKS
 
 
 def layernorm_workspace_doubles(C):

@@ -259,19 +259,6 @@ struct TailExtra {
     float* scaler_out;          // optional (N,8): the jitter that was drawn
 };
 
-// Philox4x32-10 (Salmon et al., SC'11), counter = (pose index, offset), key = seed: 4 x 32 random bits per call
-__device__ __forceinline__ void philox4x32(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1,
-                                           unsigned (&r)[4]) {
-#pragma unroll
-    for (int i = 0; i < 10; ++i) {
-        const unsigned long long p0 = 0xD2511F53ull * c0, p1 = 0xCD9E8D57ull * c2;
-        const unsigned n0 = (unsigned)(p1 >> 32) ^ c1 ^ k0, n1 = (unsigned)p1, n2 = (unsigned)(p0 >> 32) ^ c3 ^ k1, n3 = (unsigned)p0;
-        c0 = n0; c1 = n1; c2 = n2; c3 = n3;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-    r[0] = c0; r[1] = c1; r[2] = c2; r[3] = c3;
-}
-
 template <int MODE, int OUTJ, bool PREANGLE>
 __global__ __launch_bounds__(TILE) __attribute__((amdgpu_waves_per_eu((MODE == 0 && OUTJ == 16) ? 3 : 1))) void fk_forward_kernel(const float* __restrict__ in0,
                                                           const float* __restrict__ bone_len,
@@ -373,11 +360,6 @@ static_assert(T4_FRAME + TILE * 13 <= T4_X, "phase A region");
 
 __device__ __forceinline__ void t4_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
-// k / 1000 correctly rounded for the integers of the jitter draw (checked exhaustively on the host, tests/test_cpu_boundary.py)
-__device__ __forceinline__ float div1000(float k) {
-    const float q = k * 0.001f;
-    return fmaf(fmaf(-q, 1000.0f, k), 0.001f, q);
-}
 // a / b within an ulp: reciprocal + one correction step each (the IEEE sequence is ~11 instructions)
 __device__ __forceinline__ float rcp_nr(float b) {
     const float r = __builtin_amdgcn_rcpf(b);
@@ -504,14 +486,9 @@ __global__ __launch_bounds__(T4_THREADS) __attribute__((amdgpu_waves_per_eu(4, 4
         V3 p[16];
         ArmSC arm;
         // ---- before hand-over 0: sines / cosines of the role's chains; role 2 also builds the global rotation and the root,
-        // roles 2 / 3 draw the bone-length jitter (Philox4x32-10, R/models_Fk_GAN/Fk_generator.py:196-203): columns 4..7 / 0..3
+        // roles 2 / 3 draw the bone-length jitter (jitter_half, dhaug_fk_math.h): columns 4..7 / 0..3
         auto draw_half = [&](int half) {
-            const unsigned long long idx = (unsigned long long)(base + lane);
-            unsigned r[4];
-            philox4x32((unsigned)idx, (unsigned)(idx >> 32), (unsigned)ex.offset + half, (unsigned)(ex.offset >> 32),
-                       (unsigned)ex.seed, (unsigned)(ex.seed >> 32), r);
-#pragma unroll
-            for (int q = 0; q < 4; ++q) jrow[4 * half + q] = div1000((float)((int)(r[q] % 400u) - 200));
+            jitter_half((unsigned long long)(base + lane), ex.seed, ex.offset, half, jrow + 4 * half);
         };
         // legs and body: sincos of slot i sits in sc[2i], sc[2i+1] once computed; the chains run after the hand-over
         float ssc[13], csc[13];
@@ -772,7 +749,7 @@ template <typename K, typename... Args>
 int launch_tiles(K kernel, size_t lds_bytes, long long N, void* stream, Args... args) {
     if (N == 0) return DHAUG_OK;
     const long long ntiles = (N + TILE - 1) / TILE;
-    const int grid = dhaug_stream_grid(ntiles, 1, 256 * 10 * 4);
+    const int grid = dhaug_stream_grid(ntiles, 1, DHAUG_FK_MAX_BLOCKS);
     hipLaunchKernelGGL(kernel, dim3(grid), dim3(TILE), lds_bytes, (hipStream_t)stream, args..., N);
     return dhaug_launch_status();
 }
@@ -807,7 +784,7 @@ int dhaug_fk_backward(const float* angles, const float* bone_len, const float* g
     if (N == 0) return DHAUG_OK;
     DHAUG_CHECK_PTR(angles); DHAUG_CHECK_PTR(bone_len); DHAUG_CHECK_PTR(grad_out16);
     DHAUG_CHECK_PTR(grad_angles); DHAUG_CHECK_PTR(grad_bone_len); DHAUG_CHECK_PTR(grad_root);
-    DHAUG_CHECK(dhaug_aligned16(angles) && dhaug_aligned16(bone_len), DHAUG_EALIGN);
+    DHAUG_CHECK(dhaug_aligned16(angles) && dhaug_aligned16(bone_len) && dhaug_aligned16(grad_out16), DHAUG_EALIGN);
     return launch_tiles(fk_backward_kernel<0, true>, (size_t)TILE * (64 + 49) * 4, N, stream, angles, bone_len,
                         (const float*)nullptr, grad_out16, grad_angles, grad_bone_len, grad_root);
 }
@@ -817,7 +794,7 @@ int dhaug_gen_tail_forward(const float* head, const float* bone_len, const float
     DHAUG_CHECK(N >= 0, DHAUG_EINVAL);
     if (N == 0) return DHAUG_OK;
     DHAUG_CHECK_PTR(head); DHAUG_CHECK_PTR(bone_len); DHAUG_CHECK_PTR(fake16);
-    DHAUG_CHECK(dhaug_aligned16(head) && dhaug_aligned16(bone_len) && dhaug_aligned16(scaler), DHAUG_EALIGN);
+    DHAUG_CHECK(dhaug_aligned16(head) && dhaug_aligned16(bone_len) && dhaug_aligned16(scaler) && dhaug_aligned16(fake16), DHAUG_EALIGN);
     if (use_preangle)
         return launch_tiles(fk_forward_kernel<1, 16, true>, fwd_lds(37, 48), N, stream, head, bone_len, scaler, fake16,
                             angles_out);
@@ -833,7 +810,9 @@ int dhaug_gen_tail_forward_critics(const float* head, const float* bone_len, con
     DHAUG_CHECK(N >= 0, DHAUG_EINVAL);
     if (N == 0) return DHAUG_OK;
     DHAUG_CHECK_PTR(head); DHAUG_CHECK_PTR(bone_len); DHAUG_CHECK_PTR(fake16);
-    DHAUG_CHECK(dhaug_aligned16(head) && dhaug_aligned16(bone_len) && dhaug_aligned16(scaler), DHAUG_EALIGN);
+    DHAUG_CHECK(dhaug_aligned16(head) && dhaug_aligned16(bone_len) && dhaug_aligned16(scaler) && dhaug_aligned16(fake16), DHAUG_EALIGN);
+    // (optional outputs: NULL is aligned)
+    DHAUG_CHECK(dhaug_aligned16(centered) && dhaug_aligned16(kcs_bf16) && dhaug_aligned16(proj2d) && dhaug_aligned16(scaler_out), DHAUG_EALIGN);
     DHAUG_CHECK(proj2d == nullptr || (quat != nullptr && trans != nullptr && cam9 != nullptr), DHAUG_EINVAL);
     DHAUG_CHECK(!(draw_scaler && scaler != nullptr), DHAUG_EINVAL);
     TailExtra ex{};
@@ -845,7 +824,7 @@ int dhaug_gen_tail_forward_critics(const float* head, const float* bone_len, con
         for (int i = 0; i < 9; ++i) ex.c[i] = cam9[i];
     }
     const long long ntiles = (N + TILE - 1) / TILE;
-    const int grid = dhaug_stream_grid(ntiles, 1, 256 * 4 * 4);
+    const int grid = dhaug_stream_grid(ntiles, 1, DHAUG_GEN_TAIL4_MAX_BLOCKS);
     if (use_preangle)
         hipLaunchKernelGGL(gen_tail4_kernel<true>, dim3(grid), dim3(T4_THREADS), T4_FLOATS * sizeof(float), (hipStream_t)stream,
                            head, bone_len, scaler, fake16, ex, (long long)N);
@@ -860,7 +839,7 @@ int dhaug_gen_tail_backward(const float* head, const float* bone_len, const floa
     DHAUG_CHECK(N >= 0, DHAUG_EINVAL);
     if (N == 0) return DHAUG_OK;
     DHAUG_CHECK_PTR(head); DHAUG_CHECK_PTR(bone_len); DHAUG_CHECK_PTR(grad_fake16); DHAUG_CHECK_PTR(grad_head);
-    DHAUG_CHECK(dhaug_aligned16(head) && dhaug_aligned16(bone_len) && dhaug_aligned16(scaler), DHAUG_EALIGN);
+    DHAUG_CHECK(dhaug_aligned16(head) && dhaug_aligned16(bone_len) && dhaug_aligned16(scaler) && dhaug_aligned16(grad_fake16), DHAUG_EALIGN);
     const size_t lds = (size_t)TILE * (64 + 49) * 4;
     if (use_preangle)
         return launch_tiles(fk_backward_kernel<1, true>, lds, N, stream, head, bone_len, scaler, grad_fake16, grad_head,

@@ -519,6 +519,35 @@ static constexpr int kSlotCol[37] = {0, 1, 2, 3, -1, 4, 5, 6, 7, -1, 8, 9, 10, 1
 // jitter column per bone (-1: thorax, never jittered)
 static constexpr int kJitterCol[15] = {0, 0, 1, 1, 2, 2, 3, -1, 4, 4, 5, 5, 6, 6, 7};
 
+// Philox4x32-10 (Salmon et al., SC'11): counter c0..c3, key k0, k1 -> 4 x 32 random bits
+DHAUG_HD void philox4x32(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1, unsigned (&r)[4]) {
+#pragma unroll
+    for (int i = 0; i < 10; ++i) {
+        const unsigned long long p0 = 0xD2511F53ull * c0, p1 = 0xCD9E8D57ull * c2;
+        const unsigned n0 = (unsigned)(p1 >> 32) ^ c1 ^ k0, n1 = (unsigned)p1, n2 = (unsigned)(p0 >> 32) ^ c3 ^ k1, n3 = (unsigned)p0;
+        c0 = n0; c1 = n1; c2 = n2; c3 = n3;
+        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+    }
+    r[0] = c0; r[1] = c1; r[2] = c2; r[3] = c3;
+}
+// k / 1000 correctly rounded for the integers of the jitter draw, [-200, 200) (checked exhaustively on the host,
+// tests/test_cpu_boundary.py)
+DHAUG_HD float div1000(float k) {
+    const float q = k * 0.001f;
+    return fmaf(fmaf(-q, 1000.0f, k), 0.001f, q);
+}
+// Bone-length jitter of pose `idx`, columns 4 * half .. 4 * half + 3 (half in {0, 1}): one Philox call on the counter
+// (low, high word of idx; low, high word of the 64-bit sum offset + half) under the key (low, high word of seed); column
+// 4 * half + q = ((r[q] mod 400) - 200) / 1000.  R/models_Fk_GAN/Fk_generator.py:196-203 draws randint(-200, 200) / 1000.
+DHAUG_HD void jitter_half(unsigned long long idx, unsigned long long seed, unsigned long long offset, int half,
+                          float* __restrict__ out4) {
+    const unsigned long long ctr = offset + (unsigned long long)half;
+    unsigned r[4];
+    philox4x32((unsigned)idx, (unsigned)(idx >> 32), (unsigned)ctr, (unsigned)(ctr >> 32), (unsigned)seed, (unsigned)(seed >> 32), r);
+#pragma unroll
+    for (int q = 0; q < 4; ++q) out4[q] = div1000((float)((int)(r[q] % 400u) - 200));
+}
+
 // th[35] = tanh(head) (already computed).  Writes ang[37].
 template <bool PREANGLE>
 DHAUG_HD void tail_angles(const float* __restrict__ th, float* __restrict__ ang) {

@@ -2242,6 +2242,7 @@ int dhaug_gemm_tn_bf16(const uint16_t* A, int64_t lda, const uint16_t* B, int64_
 
 int dhaug_gemm_tn_bf16_rows(const uint16_t* A, int64_t lda, const uint16_t* B, int64_t ldb, float* C, int64_t ldc,
                             float* colsum_a, int64_t colsum_rows, int64_t M, int64_t N1, int64_t N2, int accumulate, void* stream) {
+    constexpr long long TN_REPRO_ROWS = 1024;                    // below: at most two slices (ops.tn_group_ok's "long batch" starts here)
     DHAUG_CHECK(colsum_rows >= 0 && colsum_rows <= M && (colsum_rows == M || colsum_rows % TF_ROWS == 0), DHAUG_EUNSUPPORTED);
     const long long cs_rows = colsum_rows == M ? (1LL << 62) : colsum_rows;
     DHAUG_CHECK(M >= 0 && N1 >= 1 && N2 >= 1, DHAUG_EINVAL);
@@ -2269,6 +2270,10 @@ int dhaug_gemm_tn_bf16_rows(const uint16_t* A, int64_t lda, const uint16_t* B, i
         if (r2 < 2 * TF_ROWS) r2 = 2 * TF_ROWS;
         sp = (M + r2 - 1) / r2;
         if (sp > 8) sp = (sp + 7) / 8 * 8;
+        if (M < TN_REPRO_ROWS && sp > 2) {                       // (see below)
+            r2 = ((M + 1) / 2 + TF_ROWS - 1) / TF_ROWS * TF_ROWS;
+            sp = (M + r2 - 1) / r2;
+        }
         constexpr int lds = 2 * (TF_ROWS * 128 + TF_ROWS * 128);
         if (const int rc = dhaug_dynamic_lds<gemm_tn64_kernel>(lds)) return rc;
         TnArgs pf{A, lda, B, ldb, C, ldc, colsum_a, M, N1, N2, r2, tiles, sp, cs_rows};
@@ -2283,6 +2288,13 @@ int dhaug_gemm_tn_bf16_rows(const uint16_t* A, int64_t lda, const uint16_t* B, i
     if (rows < 4 * BK) rows = 4 * BK;
     splits = (M + rows - 1) / rows;
     if (splits > 8) splits = (splits + 7) / 8 * 8;              // multiple of 8: XCD-local tile groups (empty slices exit)
+    // A short contraction is cut in at most two slices: two partial sums added atomically to a zeroed output give the same bits
+    // in either order (a + b = b + a), three or more do not -- the weight gradients of a small batch are then reproducible run
+    // to run (a 6 x 96-row split-operand contraction used to be cut in three).  Long batches keep the occupancy-driven split.
+    if (M < TN_REPRO_ROWS && splits > 2) {
+        rows = ((M + 1) / 2 + BK - 1) / BK * BK;
+        splits = (M + rows - 1) / rows;
+    }
     TnArgs p{A, lda, B, ldb, C, ldc, colsum_a, M, N1, N2, rows, tiles, splits, cs_rows};
     hipLaunchKernelGGL(gemm_tn_kernel, dim3((unsigned)(tiles * splits)), dim3(256), 0, s, p);
     return dhaug_launch_status();

@@ -57,7 +57,14 @@ const char* dhaug_arch(void);
  *   R/models_Fk_GAN/forward_kinematics_DH_model.py:562-822 (+ dh_matrix :80-116, rotationMatrix :141-191)
  * followed by the H36M_32_To_16_Table gather of R/models_Fk_GAN/Fk_generator.py:259.
  *   angles (N,37) deg, bone_len (N,15) m, root (N,3) m  ->  out (N,out_joints,3), out_joints in {16,32}.
- * out_joints == 32 reproduces the reference's (N,32,3) tensor exactly (unused rows = root). */
+ * out_joints == 32 reproduces the reference's (N,32,3) tensor exactly (unused rows = root).
+ * root may be NULL (= zeros).  Here and in the four entries below, every input (grad_out16 / grad_fake16 included) and the
+ * outputs out, fake16, centered, kcs_bf16, proj2d and scaler_out move as 16-byte vectors and must be 16-byte aligned
+ * (DHAUG_EALIGN, checked before the launch; optional pointers where non-NULL); the gradient outputs and angles_out need 4 bytes.
+ * One workgroup (one wave) takes tiles of 64 poses, at most DHAUG_FK_MAX_BLOCKS workgroups per launch (the four-wave
+ * dhaug_gen_tail_forward_critics: DHAUG_GEN_TAIL4_MAX_BLOCKS): more tiles, more trips of a workgroup's tile loop. */
+#define DHAUG_FK_MAX_BLOCKS 10240
+#define DHAUG_GEN_TAIL4_MAX_BLOCKS 4096
 int dhaug_fk_forward(const float* angles, const float* bone_len, const float* root, float* out,
                      int64_t N, int out_joints, void* stream);
 
@@ -86,6 +93,11 @@ int dhaug_gen_tail_forward(const float* head, const float* bone_len, const float
  * Any of the three may be NULL.  draw_scaler != 0 (scaler must be NULL): the bone-length jitter
  * `randint(-200, 200, (N, 8)) / 1000` (Fk_generator.py:196-203) is drawn inside the kernel with Philox4x32-10 keyed by
  * rng_seed, counter (pose index, rng_offset); scaler_out (N,8), if given, receives the draw.
+ *   The draw of pose i (its row index in this call, 64 bits) is two Philox calls, half h in {0, 1}:
+ *     counter c0, c1 = low, high 32 bits of i;  c2, c3 = low, high 32 bits of the 64-bit sum rng_offset + h (it wraps at 2^64);
+ *     key k0, k1 = low, high 32 bits of rng_seed;  result r[0..3].
+ *   Half 0 feeds columns 0..3, half 1 columns 4..7: column 4 h + q = ((int)(r[q] mod 400) - 200) / 1000, the division correctly
+ *   rounded in fp32.  Calls whose offsets differ by at least 2 share no counter.
  * inputs_bf16 != 0: centered and proj2d are written as bf16 (N,48) / (N,32) -- the rounding the critics' first layer
  * applies to them anyway (dhaug_mlp_forward LOAD units), at half the bytes. */
 int dhaug_gen_tail_forward_critics(const float* head, const float* bone_len, const float* scaler, float* fake16,
@@ -457,7 +469,9 @@ int dhaug_gemm_block2_stack_bf16(const uint16_t* X, int64_t ldx, const dhaug_blo
  * (split across workgroups, fp32 atomics into C).  bf16 operands, fp32 result.  `accumulate` != 0 adds
  * into C, otherwise C is overwritten (zeroed by the library on the stream first).  colsum_a (optional, fp32 [N1])
  * receives the column sums of A over M -- the bias gradient of the same layer -- computed on the matrix pipe as
- * A^T * ones by the workgroups that already hold the A tiles (same accumulate / overwrite rule as C). */
+ * A^T * ones by the workgroups that already hold the A tiles (same accumulate / overwrite rule as C).
+ * M < 1024 is cut in at most two slices: onto a zeroed C their sum is the same bits in either order, so a short contraction
+ * repeats its result run to run; a longer one (three or more atomic addends per element) may differ in the last bits. */
 int dhaug_gemm_tn_bf16(const uint16_t* A, int64_t lda, const uint16_t* B, int64_t ldb,
                        float* C, int64_t ldc, float* colsum_a, int64_t M, int64_t N1, int64_t N2, int accumulate,
                        void* stream);

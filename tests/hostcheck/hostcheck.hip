@@ -42,6 +42,26 @@ extern "C" void hostcheck_sincos(const float* x, float* s, float* c, long N) {
     for (long n = 0; n < N; ++n) sincos_rad(x[n], s[n], c[n]);
 }
 
+// the generator tail's jitter draw: the Philox block function, the correctly rounded k / 1000, and one half of a pose's draw
+extern "C" void hostcheck_philox4x32(const unsigned* counter4, const unsigned* key2, unsigned* out4, long n) {
+    for (long i = 0; i < n; ++i) {
+        unsigned r[4];
+        philox4x32(counter4[4 * i], counter4[4 * i + 1], counter4[4 * i + 2], counter4[4 * i + 3], key2[2 * i], key2[2 * i + 1], r);
+        for (int q = 0; q < 4; ++q) out4[4 * i + q] = r[q];
+    }
+}
+
+extern "C" void hostcheck_div1000(const float* k, float* out, long n) {
+    for (long i = 0; i < n; ++i) out[i] = div1000(k[i]);
+}
+
+extern "C" void hostcheck_jitter(const unsigned long long* idx, unsigned long long seed, unsigned long long offset, float* out8, long n) {
+    for (long i = 0; i < n; ++i) {
+        jitter_half(idx[i], seed, offset, 0, out8 + 8 * i);
+        jitter_half(idx[i], seed, offset, 1, out8 + 8 * i + 4);
+    }
+}
+
 // the NT dispatcher's choice: 100 * dhaug_route::NtKernel + ksteps.  wide_min_tiles < 0: the default
 extern "C" int hostcheck_nt_route(long long M, long long N, long long W, long long K, int out_bf16, int out_f32, int res_f32, int bias_ok,
                                   int mask_f32, int p8_ok, int no256, int nobig, int nop8, long long wide_min_tiles) {

@@ -51,6 +51,34 @@ def test_scratch_sizes_mirror_the_header(built):
     assert eval(expr) == fused.X3_WORKSPACE_BYTES
 
 
+def test_fk_grid_caps_mirror_the_header(built):
+    """the workgroup caps of the FK launches: header, source and the binding's mirror agree (tests/test_gpu_fk_tail.py computes its
+    multi-pass sizes from the mirror: a changed cap cannot silently make those tests single-pass)"""
+    import dhaug_amd
+    lib = dhaug_amd._lib
+    hdr = open(os.path.join(ROOT, "include", "dhaug.h")).read()
+    src = open(os.path.join(os.path.dirname(lib.__file__), "csrc", "dhaug_fk.hip")).read()
+    define = lambda n: int(re.search(r"#define\s+%s\s+(\d+)" % n, hdr).group(1))
+    assert define("DHAUG_FK_MAX_BLOCKS") == lib.FK_MAX_BLOCKS == 10240
+    assert define("DHAUG_GEN_TAIL4_MAX_BLOCKS") == lib.GEN_TAIL4_MAX_BLOCKS == 4096
+    assert src.count("dhaug_stream_grid(ntiles, 1, DHAUG_FK_MAX_BLOCKS)") == 1                      # launch_tiles: the four one-wave entries
+    assert src.count("dhaug_stream_grid(ntiles, 1, DHAUG_GEN_TAIL4_MAX_BLOCKS)") == 1               # the four-wave generator tail
+    assert len(re.findall(r"dhaug_stream_grid\(", src)) == 2 and "constexpr int TILE = 64;" in src
+
+
+def test_div1000_is_the_correctly_rounded_quotient(built):
+    """div1000 (csrc/dhaug_fk_math.h), exhaustively over the integers of the jitter draw: k / 1000 as IEEE fp32 division gives it"""
+    import numpy as np
+    lib = ctypes.CDLL(os.path.join(ROOT, "tests", "hostcheck", "_build", "libhostcheck.so"))
+    k = np.arange(-200, 200, dtype=np.float32)
+    out = np.full_like(k, 7.0)
+    P = ctypes.POINTER(ctypes.c_float)
+    lib.hostcheck_div1000(k.ctypes.data_as(P), out.ctypes.data_as(P), ctypes.c_long(len(k)))
+    want = k / np.float32(1000)
+    assert want.dtype == np.float32 and len(k) == 400
+    assert np.array_equal(out.view(np.uint32), want.view(np.uint32))
+
+
 def test_ablation_switches_need_an_ablation_build(tmp_path):
     """a development switch ("timing only, results wrong") cannot reach a product library: every such -D is a compile error
     without -DDHAUG_ABLATION_BUILD (csrc/dhaug_common.h), and build_lib ignores DHAUG_EXTRA_HIPFLAGS unless the environment
@@ -96,6 +124,26 @@ def test_argument_errors_are_returned_not_thrown(built):
     mis = ctypes.c_void_p(ctypes.addressof(buf) + 4)
     assert L.dhaug_fk_forward(mis, mis, mis, mis, 1, 16, None) == -2                 # misaligned
     assert L.dhaug_gemm_bf16(mis, 8, mis, 8, None, None, 0, None, 0, None, 0, 0, None, 0, 4, 4, 24, 0, 0.0, None) in (-1, -3)
+    # every pointer of the FK entries that moves as 16-byte vectors, one misaligned call each; the others are aligned HOST addresses,
+    # so a call that got as far as a launch would return a HIP error, not -2
+    fkb = (ctypes.c_float * 1024)()
+    al = ctypes.c_void_p((ctypes.addressof(fkb) + 15) & ~15)
+    for off in (4, 8):
+        m = ctypes.c_void_p(al.value + off)
+        assert L.dhaug_fk_backward(al, al, m, al, al, al, 1, None) == -2                                  # grad_out16
+        assert L.dhaug_gen_tail_backward(al, al, al, m, al, 1, 1, None) == -2                             # grad_fake16
+        assert L.dhaug_gen_tail_backward(al, al, None, m, al, 1, 0, None) == -2
+        assert L.dhaug_gen_tail_forward(al, al, al, m, al, 1, 1, None) == -2                              # fake16
+        assert L.dhaug_gen_tail_forward(al, al, None, m, None, 1, 0, None) == -2
+        crit = lambda fake=al, cen=al, kcs=al, proj=al, so=None, draw=0: L.dhaug_gen_tail_forward_critics(
+            al, al, None, fake, cen, kcs, al, al, al, proj, draw, 1, 2, so, 1, 1, 0, None)
+        assert crit(fake=m) == -2 and crit(cen=m) == -2 and crit(kcs=m) == -2 and crit(proj=m) == -2
+        assert crit(so=m, draw=1) == -2 and crit(so=m) == -2                                              # scaler_out, drawn or not
+        assert crit(fake=m, cen=None, kcs=None, proj=None) == -2 and crit(cen=m, kcs=None, proj=None) == -2
+    m2 = ctypes.c_void_p(al.value + 2)
+    assert L.dhaug_gen_tail_forward_critics(al, al, None, al, None, m2, None, None, None, None, 0, 0, 0, None, 1, 1, 1, None) == -2
+    assert L.dhaug_gen_tail_forward_critics(al, al, al, al, al, al, None, None, None, None, 1, 0, 0, None, 1, 1, 0, None) == -1   # draw and scaler
+    assert L.dhaug_gen_tail_forward_critics(al, al, None, al, al, al, None, None, None, al, 0, 0, 0, None, 1, 1, 0, None) == -1   # proj2d, no camera
     # the round-6 entries: argument checks of the planes products and of the contraction's planes fields (no launch is reached)
     big = (ctypes.c_float * 4096)()
     a16 = ctypes.c_void_p((ctypes.addressof(big) + 15) & ~15)

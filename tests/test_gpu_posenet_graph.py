@@ -141,15 +141,11 @@ CONFIGS = [(n, p, "mse") for n in ("videopose", "mlp", "mulit_farme_videopose", 
 # --------------------------------------------------------------------------------------------------- 1. equal to the eager path
 @pytest.mark.parametrize("name,prec,crit", CONFIGS)
 def test_graph_run_equals_the_eager_run(M, name, prec, crit):
-    """Measured (MI355X, gfx950, 2026-10-20, two runs of this file): in nine of the ten configurations two graph=False runs agree bit
-    for bit in every tensor, and so does the graph run.  In gcn-bf16x6 they do not (its weight-gradient GEMM contracts 6 x 96 rows and
-    splits them over workgroups that add with atomics): largest eager-eager distance 4.1e-03 (a SemGraphConv bias in front of a
-    BatchNorm, whose gradient is rounding residue that Adam turns into steps of lr), running means 5e-04 .. 1.5e-03, weights and e
-    1.5e-08 .. 1.2e-07, losses 9.5e-07; graph-eager distances lie in the same ranges (largest 4.4e-03).  There a tensor that moves
-    by one ulp between runs has a distance of 0 or of 3e-08 .. 1.2e-07 by chance: in seven of eight measured runs one to three tensors
-    (an e vector, a BatchNorm weight, a running variance) had eager-eager 0 and graph-eager 3.0e-08 .. 1.2e-07 and failed the rule
-    below, in one run every tensor passed.  The rule is kept as it is stated; in that one configuration it fails more often than not
-    without anything being wrong with the captured step -- a third graph=False run would miss it against the first just as often."""
+    """Measured (MI355X, gfx950, 2026-10-20, two runs of this file): in all ten configurations two graph=False runs agree bit for bit
+    in every tensor, and so does the graph run.  gcn-bf16x6 used not to: its weight-gradient GEMM contracts 6 x 96 rows, which
+    dhaug_gemm_tn_bf16_rows cut in three slices that add with atomics (eager-eager distances up to 4.1e-03, and a tensor that moved
+    by one ulp missed the rule below by chance in seven of eight runs).  A contraction of fewer than 1 024 rows is now cut in at most
+    two slices, whose sum onto a zeroed output does not depend on their order."""
     (ea, sa, _), (eb, sb, _), (gr, sg, _) = three_runs(M, name, prec, crit)
     assert set(sa) == set(sb) == set(sg)
     worst = 0.0
