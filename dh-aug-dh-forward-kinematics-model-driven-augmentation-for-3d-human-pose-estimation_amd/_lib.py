@@ -32,6 +32,8 @@ SIGNATURES = {
     "dhaug_clip_pair_batch": [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp,
                               _vp, _vp],
     "dhaug_pose_metrics": [_vp, _vp, _i64, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp],
+    "dhaug_pose_column_errors": [_vp, _vp, _i64, _i64, _i32, _vp, _vp, _vp, _vp],
+    "dhaug_pose_scaled_errors": [_vp, _vp, _i64, _i32, _vp, _i32, _vp, _vp, _vp],
     "dhaug_pair_batch": [_vp, _vp, _i64, _i32, _i32, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "dhaug_pose_mse": [_vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp],
     "dhaug_pose_mpjpe": [_vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp],
@@ -199,6 +201,12 @@ EVAL_MAX_THRESHOLDS = 32
 EVAL_MAX_MULTIPLICITY = 1024
 EVAL_TOTALS_WORDS = 3 + EVAL_MAX_THRESHOLDS            # struct dhaug_eval_totals as int64 words
 EVAL_WORKSPACE_BYTES = 2048 * EVAL_TOTALS_WORDS * 8
+COLERR_MAX_COLS = 16 * 243                             # DHAUG_COLERR_MAX_COLS
+COLERR_MAX_BLOCKS = 1024                               # DHAUG_COLERR_MAX_BLOCKS
+COLERR_MIN_STEPS = 4                                   # DHAUG_COLERR_MIN_STEPS
+COLERR_WORKSPACE_BYTES = (COLERR_MAX_BLOCKS + COLERR_MAX_BLOCKS * 1024) * 8
+SCALEDERR_MAX_BLOCKS = 2048                            # DHAUG_SCALEDERR_MAX_BLOCKS
+SCALEDERR_WORKSPACE_BYTES = SCALEDERR_MAX_BLOCKS * 2 * 8
 LOSS_METER_WORDS = 3                                   # struct dhaug_loss_meter as int64 words (word 0: fp64 bits)
 POSETRAIN_WORKSPACE_BYTES = 2048 * 8
 

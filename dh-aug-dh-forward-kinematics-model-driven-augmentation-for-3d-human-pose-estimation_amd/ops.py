@@ -357,6 +357,66 @@ def pose_metrics(pred, target, center=False, thresholds=(), multiplicity=None, p
     return mp, pp
 
 
+def _f64_sums(t, n, name, what):
+    assert t.is_cuda and t.dtype == torch.float64 and t.numel() == n and t.is_contiguous(), \
+        "%s: %s must be a contiguous fp64 device tensor of %d elements" % (name, what, n)
+    return t
+
+
+def pose_column_errors(pred, target, center=False, col_sums=None, vel_sum=None):
+    """per-column sums of the joint error and the velocity-error sum of (rows, ..., 3) joints (dhaug_pose_column_errors): the
+    first axis is the rows, the axes between it and the last one are flattened into the columns.  col_sums: fp64 (cols,)
+    device tensor, += the sum over the rows of |pred - target| per column; vel_sum: fp64 (1,) device tensor, += the sum over
+    consecutive row pairs and columns of |diff(pred) - diff(target)|.  Both are accumulated into (stream order, no host read);
+    at least one must be given.  center: each group of 16 columns is root-centred first.  Returns (col_sums, vel_sum)."""
+    name = "pose_column_errors"
+    if tuple(pred.shape) != tuple(target.shape):
+        raise ValueError("%s: pred %s and target %s differ in shape" % (name, tuple(pred.shape), tuple(target.shape)))
+    if pred.dim() < 2 or pred.shape[-1] != 3:
+        raise ValueError("%s: joints must be (rows, ..., 3), got %s" % (name, tuple(pred.shape)))
+    if col_sums is None and vel_sum is None:
+        raise ValueError("%s: nothing to compute (no col_sums and no vel_sum)" % name)
+    rows, cols = pred.shape[0], 1
+    for d in pred.shape[1:-1]:
+        cols *= d
+    if cols % 4 or cols > _lib.COLERR_MAX_COLS or (center and cols % 16):
+        raise ValueError("%s: %d columns: need a multiple of %d, at most %d" % (name, cols, 16 if center else 4, _lib.COLERR_MAX_COLS))
+    y = _dev(pred, torch.float32, name)
+    x = _dev(target, torch.float32, name)
+    if col_sums is not None:
+        _f64_sums(col_sums, cols, name, "col_sums")
+    if vel_sum is not None:
+        _f64_sums(vel_sum, 1, name, "vel_sum")
+    ws = torch.empty(_lib.COLERR_WORKSPACE_BYTES // 8, dtype=torch.float64, device=y.device)
+    _lib.call("dhaug_pose_column_errors", _p(y), _p(x), rows, cols, int(bool(center)), _p(col_sums), _p(vel_sum), _p(ws), _stream())
+    return col_sums, vel_sum
+
+
+def pose_scaled_errors(pred, target, center=False, w=None, sums=None):
+    """the N-MPJPE and weighted error sums of (..., 16, 3) poses (dhaug_pose_scaled_errors).  sums: fp64 (2,) device tensor
+    accumulated into (a zeroed one is made when None): sums[0] += the sum of |s pred - target| over all joints, s the pose's
+    least-squares scale; sums[1] += the sum of w |pred - target|, w fp32 with one value per pose (P elements) or per joint
+    (16 P elements), untouched without w.  Returns sums."""
+    name = "pose_scaled_errors"
+    if tuple(pred.shape) != tuple(target.shape):
+        raise ValueError("%s: pred %s and target %s differ in shape" % (name, tuple(pred.shape), tuple(target.shape)))
+    if pred.dim() < 2 or tuple(pred.shape[-2:]) != (16, 3):
+        raise ValueError("%s: poses must be (..., 16, 3), got %s" % (name, tuple(pred.shape)))
+    P = pred.numel() // 48
+    if w is not None and w.numel() not in (P, 16 * P):
+        raise ValueError("%s: w must hold one value per pose (%d) or per joint (%d), got %s" % (name, P, 16 * P, tuple(w.shape)))
+    y = _dev(pred, torch.float32, name)
+    x = _dev(target, torch.float32, name)
+    per_joint = w is not None and P > 0 and w.numel() == 16 * P
+    wd = None if w is None else _dev(w, torch.float32, name)
+    if sums is None:
+        sums = torch.zeros(2, dtype=torch.float64, device=y.device)
+    _f64_sums(sums, 2, name, "sums")
+    ws = torch.empty(_lib.SCALEDERR_WORKSPACE_BYTES // 8, dtype=torch.float64, device=y.device)
+    _lib.call("dhaug_pose_scaled_errors", _p(y), _p(x), P, int(bool(center)), _p(wd), int(per_joint), _p(sums), _p(ws), _stream())
+    return sums
+
+
 def center_flip(x, center, flip, adjoint=False):
     C = x.shape[-1]
     v = _dev(x, torch.float32, "center_flip").reshape(-1, 16 * C)

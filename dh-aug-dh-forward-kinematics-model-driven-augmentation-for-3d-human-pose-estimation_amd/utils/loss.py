@@ -121,6 +121,194 @@ def compute_AUC(gts, preds, scales=1000, eval_joints=None):
     return (tot[3:3 + len(AUC_THRESHOLDS)].double() * 100.0 / (tot[2].double() * cols)).mean()
 
 
+# ------------------------------------------------------------------------------------------------------------------------
+# The VideoPose3D family of R/utils/loss.py: mpjpe_byjoint :17-23, weighted_mpjpe :26-32, n_mpjpe :167-177 and
+# mean_velocity_error :180-189, on dhaug_pose_column_errors / dhaug_pose_scaled_errors.  The module's conventions hold: poses
+# are (..., 16, 3), host inputs are uploaded as fp32 and one host read returns the reference's type, device tensors in give
+# device tensors out with no synchronisation.  Every distance, scale and sum is fp64 from the fp32 values; the result is
+# rounded once to the returned type.  The kernels are metrics, not criteria: when `predicted` requires grad (and gradients
+# are enabled) the three torch functions evaluate the reference's expression in plain torch instead, so training code that
+# uses them as a loss keeps working.
+
+
+def _check_pair(pred, target, name):
+    """the shape checks of _device_pair alone; returns the shape"""
+    sp, st = tuple(pred.shape), tuple(target.shape)
+    if sp != st:
+        raise ValueError("%s: predicted %s and target %s differ in shape" % (name, sp, st))
+    if len(sp) < 2 or sp[-2:] != (16, 3):
+        raise ValueError("%s: poses must be (..., 16, 3), got %s" % (name, sp))
+    return sp
+
+
+def _shaped_pair(pred, target, name):
+    """_device_pair with the callers' shape kept: (pred, target, host)"""
+    y, x, host = _device_pair(pred, target, name)
+    shape = tuple(pred.shape)
+    return y.reshape(shape), x.reshape(shape), host
+
+
+def _joints(shape):
+    """the number of joints of a (..., 16, 3) shape"""
+    return int(np.prod(shape[:-1], dtype=np.int64))
+
+
+def _check_columns(shape, name):
+    """dhaug_pose_column_errors takes the axes between the first and the last as its columns"""
+    if _joints(shape[1:]) > _lib.COLERR_MAX_COLS:
+        raise ValueError("%s: %d joints per entry of the first axis, at most %d" % (name, _joints(shape[1:]), _lib.COLERR_MAX_COLS))
+
+
+def _wants_grad(predicted):
+    return torch.is_tensor(predicted) and predicted.requires_grad and torch.is_grad_enabled()
+
+
+def _result(v, predicted, host):
+    """v (fp64 device tensor) as the torch functions return it: predicted's floating dtype, on the host for host inputs"""
+    dtype = predicted.dtype if torch.is_tensor(predicted) else torch.float32
+    v = v.to(dtype if dtype.is_floating_point else torch.float32)
+    return v.cpu() if host else v
+
+
+def mpjpe_byjoint(predicted, target):
+    """the joint error averaged over the FIRST axis only: (N, 16, 3) gives (16,), (B, F, 16, 3) gives (F, 16) -- the shape is
+    predicted.shape[1:-1].  fp64 distances and sums (dhaug_pose_column_errors).  A `predicted` that requires grad is evaluated
+    in plain torch (differentiable), not on the kernel."""
+    sp = _check_pair(predicted, target, "mpjpe_byjoint")
+    if _wants_grad(predicted):
+        return torch.mean(torch.norm(predicted - target.to(predicted.device), dim=-1), dim=0)
+    if len(sp) == 2:                                  # one pose: the first axis is the joints
+        return mpjpe(predicted, target)
+    _check_columns(sp, "mpjpe_byjoint")
+    y, x, host = _shaped_pair(predicted, target, "mpjpe_byjoint")
+    cols = torch.zeros(_joints(sp[1:]), dtype=torch.float64, device=y.device)
+    ops.pose_column_errors(y, x, col_sums=cols)
+    return _result((cols / float(sp[0])).reshape(sp[1:-1]), predicted, host)
+
+
+def _weights(w, shape, name):
+    """w against the joint-error shape (predicted.shape[:-1]) under torch broadcasting, checked; w stays as given in
+    the per-pose (..., 1) and per-joint forms, any other broadcastable form is expanded to one value per joint"""
+    ws = tuple(w.shape)
+    if len(ws) == 0 or ws[0] != shape[0]:
+        raise ValueError("%s: w %s must have predicted's first dimension (%d)" % (name, ws, shape[0]))
+    try:
+        out = tuple(torch.broadcast_shapes(ws, shape))
+    except RuntimeError:
+        raise ValueError("%s: w %s does not broadcast against the joint errors %s" % (name, ws, shape)) from None
+    if out != shape:
+        raise ValueError("%s: w %s would enlarge the joint errors %s to %s" % (name, ws, shape, out))
+    if ws == shape or ws == shape[:-1] + (1,):
+        return w
+    return w.expand(shape)
+
+
+def weighted_mpjpe(predicted, target, w):
+    """mean(w * norm(predicted - target, dim=-1)) under torch broadcasting of w against predicted.shape[:-1]: one weight per
+    joint, per pose ((..., 1)), or any shape that broadcasts to these without enlarging the result; w.shape[0] must be
+    predicted.shape[0].  Weights of any sign.  fp64 distances and sums (dhaug_pose_scaled_errors).  A `predicted` that requires
+    grad is evaluated in plain torch (differentiable), not on the kernel."""
+    sp = _check_pair(predicted, target, "weighted_mpjpe")
+    w = _weights(w if torch.is_tensor(w) else torch.from_numpy(np.ascontiguousarray(w)), sp[:-1], "weighted_mpjpe")
+    if _wants_grad(predicted):
+        return torch.mean(w.to(predicted.device) * torch.norm(predicted - target.to(predicted.device), dim=-1))
+    y, x, host = _shaped_pair(predicted, target, "weighted_mpjpe")
+    sums = ops.pose_scaled_errors(y, x, w=w.detach().to(device=y.device, dtype=torch.float32))
+    return _result(sums[1] / float(_joints(sp)), predicted, host)
+
+
+def n_mpjpe(predicted, target):
+    """scale-normalised MPJPE of (B, F, 16, 3) poses: per frame s = mean_j(sum target * predicted) / mean_j(sum predicted^2),
+    then mpjpe(s * predicted, target).  fp64 scale, distances and sums (dhaug_pose_scaled_errors); an all-zero predicted frame
+    gives NaN, as the reference.  A `predicted` that requires grad is evaluated in plain torch (differentiable), not on the
+    kernel."""
+    if len(tuple(predicted.shape)) != 4:
+        raise ValueError("n_mpjpe: poses must be (B, F, 16, 3), got %s" % (tuple(predicted.shape),))
+    sp = _check_pair(predicted, target, "n_mpjpe")
+    if _wants_grad(predicted):
+        target = target.to(predicted.device)
+        norm_predicted = torch.mean(torch.sum(predicted ** 2, dim=3, keepdim=True), dim=2, keepdim=True)
+        norm_target = torch.mean(torch.sum(target * predicted, dim=3, keepdim=True), dim=2, keepdim=True)
+        return torch.mean(torch.norm(norm_target / norm_predicted * predicted - target, dim=-1))
+    y, x, host = _shaped_pair(predicted, target, "n_mpjpe")
+    sums = ops.pose_scaled_errors(y, x)
+    return _result(sums[0] / float(_joints(sp)), predicted, host)
+
+
+def mean_velocity_error(predicted, target):
+    """mean per-joint velocity error of a sequence (frames, ..., 16, 3): mean(norm(diff(predicted, axis=0) - diff(target,
+    axis=0), axis=-1)), fp64 differences, distances and sums (dhaug_pose_column_errors).  Host inputs (numpy or CPU tensors):
+    a numpy scalar, float32 when both inputs are fp32, else float64.  Device tensors: a 0-d device tensor.  Fewer than two
+    frames give NaN without a launch."""
+    sp = _check_pair(predicted, target, "mean_velocity_error")
+    if len(sp) < 3:
+        raise ValueError("mean_velocity_error: a sequence must be (frames, ..., 16, 3), got %s" % (sp,))
+    _check_columns(sp, "mean_velocity_error")
+    host = not (torch.is_tensor(predicted) and predicted.is_cuda)
+    both32 = all(getattr(a, "dtype", None) in (np.float32, torch.float32) for a in (predicted, target))
+    if sp[0] < 2:
+        if host:
+            return (np.float32 if both32 else np.float64)(np.nan)
+        return torch.full((), float("nan"), dtype=predicted.dtype if predicted.dtype.is_floating_point else torch.float32,
+                          device=predicted.device)
+    y, x, host = _shaped_pair(predicted, target, "mean_velocity_error")
+    vel = ops.pose_column_errors(y, x, vel_sum=torch.zeros(1, dtype=torch.float64, device=y.device))[1]
+    v = vel[0] / float((sp[0] - 1) * _joints(sp[1:]))
+    if not host:
+        return v.to(predicted.dtype if predicted.dtype.is_floating_point else torch.float32)
+    return (np.float32 if both32 else np.float64)(v.item())
+
+
+class PoseDetailAccumulator:
+    """per-joint MPJPE, N-MPJPE and the velocity error summed over batches in one device record; result() reads it once.
+
+    center=True root-centres both poses first (what evaluate does).  add() enqueues its launches on the current stream and
+    never synchronises; the counts (poses, velocity pairs) follow from the shapes and are kept on the host."""
+
+    def __init__(self, device=None, center=True):
+        self.center = bool(center)
+        self.record = torch.zeros(19, dtype=torch.float64, device=device if device is not None else "cuda")
+        self.poses = 0
+        self.velocity_pairs = 0
+
+    def zero(self):
+        self.record.zero_()
+        self.poses = self.velocity_pairs = 0
+        return self
+
+    def add(self, pred, target, sequence=False):
+        """(..., 16, 3) poses.  sequence=True: the first axis is the frames of ONE sequence, whose velocity error is accumulated
+        too (one call per sequence: no pair is formed across calls)."""
+        y, x, _ = _shaped_pair(pred, target, "PoseDetailAccumulator.add")
+        col, nm, vel = self.record[:16], self.record[16:18], self.record[18:]
+        y3, x3 = y.reshape(-1, 16, 3), x.reshape(-1, 16, 3)
+        pairs = 0
+        if sequence:
+            if y.dim() < 3:
+                raise ValueError("PoseDetailAccumulator.add: a sequence must be (frames, ..., 16, 3), got %s" % (tuple(y.shape),))
+            pairs = max(0, y.shape[0] - 1) * (y[0].numel() // 3)
+        if y3.shape[0] == 0:
+            return
+        if sequence and y.dim() == 3:
+            ops.pose_column_errors(y3, x3, center=self.center, col_sums=col, vel_sum=vel)
+        else:
+            ops.pose_column_errors(y3, x3, center=self.center, col_sums=col)
+            if pairs:
+                ops.pose_column_errors(y, x, center=self.center, vel_sum=vel)
+        ops.pose_scaled_errors(y3, x3, center=self.center, sums=nm)
+        self.poses += y3.shape[0]
+        self.velocity_pairs += pairs
+
+    def result(self):
+        """dict(poses, mpjpe_byjoint (16 floats), n_mpjpe, velocity in meters, velocity_pairs) from one host read; zeros where
+        nothing was added"""
+        t = self.record.cpu().numpy()
+        n, pairs = self.poses, self.velocity_pairs
+        return dict(poses=n, mpjpe_byjoint=[float(v) / n if n else 0.0 for v in t[:16]],
+                    n_mpjpe=float(t[16]) / (16.0 * n) if n else 0.0,
+                    velocity=float(t[18]) / pairs if pairs else 0.0, velocity_pairs=pairs)
+
+
 class PoseMetricsAccumulator:
     """MPJPE, P-MPJPE, PCK (150 mm) and AUC summed over batches in one device record; result() reads it once.
 

@@ -274,6 +274,47 @@ int dhaug_pose_metrics(const float* pred, const float* target, int64_t P, int ce
                        const int32_t* multiplicity, float* mpjpe_out, float* pmpjpe_out, void* totals, void* workspace,
                        void* stream);
 
+/* The detailed pose errors of R/utils/loss.py: mpjpe_byjoint :17-23, weighted_mpjpe :26-32, n_mpjpe :167-177 and
+ * mean_velocity_error :180-189 (numpy).  Both entries: fp32 inputs, 16-byte aligned (DHAUG_EALIGN); center != 0 subtracts the
+ * first joint of every group of 16 joints in fp32, as dhaug_pose_metrics does; every difference, square, square root and sum
+ * after that in fp64 from the fp32 values.  Sums are ACCUMULATED into caller-zeroed device doubles.  Deterministic: per-workgroup
+ * fp64 partials in the workspace, added in a fixed order by a second launch, no atomics; the same call sequence gives the same
+ * bits.  workspace: device, 8-byte aligned, one call at a time per workspace (stream order).
+ *
+ * dhaug_pose_column_errors: pred / target (rows, cols, 3), cols a multiple of 4 and <= DHAUG_COLERR_MAX_COLS (16 joints x 243
+ *   frames).  With e[r,c] = |pred[r,c] - target[r,c]|:
+ *     col_sums: optional device double[cols], col_sums[c] += sum over r of e[r,c]  (mpjpe_byjoint = col_sums / rows);
+ *     vel_sum:  optional device double[1], += sum over r < rows - 1 and c of
+ *               |(pred[r+1,c] - pred[r,c]) - (target[r+1,c] - target[r,c])|  (mean_velocity_error = vel_sum / ((rows - 1) cols));
+ *               rows = 1 has no such pair and leaves it untouched.
+ *   A workgroup owns a slab of consecutive rows and walks it downwards; the partition into slabs is a function of (rows, cols)
+ *   only: with RG = max(1, 1024 / cols) rows per step (1 for cols > 1024) and CC = ceil(cols / 1024) workgroups per row,
+ *   at most DHAUG_COLERR_MAX_BLOCKS / CC slabs of at least DHAUG_COLERR_MIN_STEPS steps.  workspace: DHAUG_COLERR_WORKSPACE_BYTES.
+ *   DHAUG_EINVAL: rows or cols < 0, neither col_sums nor vel_sum, NULL workspace, center != 0 with cols % 16 != 0, or (rows, cols
+ *   > 0) a NULL pred / target.  DHAUG_EUNSUPPORTED: cols > DHAUG_COLERR_MAX_COLS, cols % 4 != 0, rows >= 2^31.  DHAUG_EALIGN also:
+ *   col_sums, vel_sum or workspace not 8-byte aligned.  rows = 0 or cols = 0 is a no-op.
+ *
+ * dhaug_pose_scaled_errors: pred / target P poses of (16, 3).  sums: device double[2]:
+ *     sums[0] += sum over poses p and joints j of |s_p pred_pj - target_pj|, s_p = (sum_j target_pj . pred_pj) / (sum_j pred_pj .
+ *               pred_pj) in fp64 (n_mpjpe = sums[0] / (16 P)); an all-zero predicted pose gives 0 / 0 = NaN, as the reference;
+ *     sums[1] += sum over p, j of w e_pj, e_pj = |pred_pj - target_pj| (weighted_mpjpe = sums[1] / (16 P)): w optional fp32, one
+ *               value per joint (w_per_joint != 0: P x 16 values, 16-byte aligned) or per pose (P values, 4-byte aligned), any
+ *               sign; with w == NULL sums[1] is untouched.
+ *   workspace: DHAUG_SCALEDERR_WORKSPACE_BYTES.
+ *   DHAUG_EINVAL: P < 0, NULL sums / workspace, (P > 0) a NULL pred / target.  DHAUG_EUNSUPPORTED: P >= 2^31.  DHAUG_EALIGN also:
+ *   sums or workspace not 8-byte aligned.  P = 0 is a no-op.
+ * Two launches each (errors, then the reduction of the partials). */
+#define DHAUG_COLERR_MAX_COLS (16 * 243)
+#define DHAUG_COLERR_MAX_BLOCKS 1024
+#define DHAUG_COLERR_MIN_STEPS 4
+#define DHAUG_COLERR_WORKSPACE_BYTES ((DHAUG_COLERR_MAX_BLOCKS + DHAUG_COLERR_MAX_BLOCKS * 1024) * 8)
+#define DHAUG_SCALEDERR_MAX_BLOCKS 2048
+#define DHAUG_SCALEDERR_WORKSPACE_BYTES (DHAUG_SCALEDERR_MAX_BLOCKS * 2 * 8)
+int dhaug_pose_column_errors(const float* pred, const float* target, int64_t rows, int64_t cols, int center, double* col_sums,
+                             double* vel_sum, void* workspace, void* stream);
+int dhaug_pose_scaled_errors(const float* pred, const float* target, int64_t P, int center, const float* w, int w_per_joint,
+                             double* sums, void* workspace, void* stream);
+
 /* Posenet training: everything around the posenet call of train_posenet (R/function_aug/model_pos_train.py:13-83),
  * video_mode_train_posenet and GAN_dataSet_video_mode_train_posenet (R/models_Fk_GAN/video_mode_operate.py:532-765).
  *
