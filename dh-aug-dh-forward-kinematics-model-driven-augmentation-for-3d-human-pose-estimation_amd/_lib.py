@@ -41,6 +41,9 @@ SIGNATURES = {
     "dhaug_adam_clip_step": [_vp, _vp, _vp, _vp, _i64, _f32, _f32, _f32, _f32, _vp, _f32, _f32, _vp, _vp, _vp],
     "dhaug_adam_clip_step_lr": [_vp, _vp, _vp, _vp, _i64, _vp, _f32, _f32, _f32, _vp, _f32, _f32, _vp, _vp, _vp],
     "dhaug_u64_add": [_vp, _u64, _vp],
+    "dhaug_pose_nmpjpe": [_vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp],
+    "dhaug_pose_wmpjpe": [_vp, _vp, _i64, _vp, _i32, _i64, _vp, _vp, _vp, _vp, _vp],
+    "dhaug_pose_byjoint_backward": [_vp, _vp, _i64, _i64, _vp, _vp, _vp],
     "dhaug_gemm_bf16_dmask": [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _i32, _f32, _vp, _i64, _i64, _i64, _i64, _vp],
     "dhaug_gemm_bf16_dmask_pad": [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _i32, _f32, _vp, _i64, _i64, _i64, _i64, _i64, _vp],
     "dhaug_gemm_bf16_dbits": [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _i32, _f32, _vp, _i64, _i64, _vp],
@@ -209,6 +212,7 @@ SCALEDERR_MAX_BLOCKS = 2048                            # DHAUG_SCALEDERR_MAX_BLO
 SCALEDERR_WORKSPACE_BYTES = SCALEDERR_MAX_BLOCKS * 2 * 8
 LOSS_METER_WORDS = 3                                   # struct dhaug_loss_meter as int64 words (word 0: fp64 bits)
 POSETRAIN_WORKSPACE_BYTES = 2048 * 8
+WMPJPE_PER_POSE, WMPJPE_PER_JOINT, WMPJPE_SHARED = 1, 2, 3   # DHAUG_WMPJPE_*: the w_mode of dhaug_pose_wmpjpe
 
 ERRORS = {-1: "DHAUG_EINVAL (bad argument)", -2: "DHAUG_EALIGN (alignment contract violated)",
           -3: "DHAUG_EUNSUPPORTED (shape not implemented)"}

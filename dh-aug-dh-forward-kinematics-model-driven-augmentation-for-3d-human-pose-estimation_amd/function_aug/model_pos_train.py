@@ -8,6 +8,7 @@ The posenet is whatever nn.Module the caller passes; what runs in this package's
   * nn.MSELoss(reduction='mean'): dhaug_pose_mse gives the loss, its gradient (the loop calls outputs.backward(grad)) and the
     epoch's loss meter, AverageMeter.update(loss, num_poses) on the device;
   * utils.loss.mpjpe of this package (the criterion of the reference's video command): dhaug_pose_mpjpe, the same way;
+  * utils.loss.n_mpjpe and any utils.loss.JointWeightedMpjpe instance: dhaug_pose_nmpjpe / dhaug_pose_wmpjpe, the same way;
   * nn.utils.clip_grad_norm_(max_norm=1) + optimizer.step(): optimizer.clip_step(1) of optim.PosenetAdam, two launches.
 Each piece falls back on its own to what the reference calls (criterion(...).backward(), clip_grad_norm_, optimizer.step() of a
 stock torch optimizer) when it does not apply; the loss still goes to the meter on the device.  Nothing is read on the host per
@@ -29,7 +30,7 @@ import torch.nn as nn
 from .. import autograd_ops as A
 from .. import ops
 from ..optim import PosenetAdam
-from ..utils.loss import mpjpe
+from ..utils.loss import JointWeightedMpjpe, mpjpe, n_mpjpe
 
 METERS = ("loss", "flip_loss", "back_loss", "back_flip_loss")
 # DHAUG_POSENET_GRAPH=1: the three loops replay the posenet step as a hipGraph without being asked through args (read once, here)
@@ -51,6 +52,22 @@ def set_grad(nets, requires_grad=False):
 def graph_requested(args):
     """what the three loops pass as StepRunner's graph: args.posenet_graph, or DHAUG_POSENET_GRAPH=1; off by default"""
     return bool(getattr(args, "posenet_graph", False)) or POSENET_GRAPH
+
+
+def fused_criterion(criterion):
+    """the name of the fused loss + gradient launch pair a criterion stands for, or None (the generic path: criterion(outputs,
+    targets).backward()).  Four are fused: nn.MSELoss(reduction='mean') -> "mse", and of this package's utils.loss the functions
+    mpjpe -> "mpjpe" and n_mpjpe -> "n_mpjpe" themselves (identity, not equality of results) and any JointWeightedMpjpe instance
+    -> "wmpjpe".  Decided from the object alone, before any GPU work."""
+    if isinstance(criterion, nn.MSELoss):
+        return "mse" if criterion.reduction == "mean" else None
+    if criterion is mpjpe:
+        return "mpjpe"
+    if criterion is n_mpjpe:
+        return "n_mpjpe"
+    if isinstance(criterion, JointWeightedMpjpe):
+        return "wmpjpe"
+    return None
 
 
 def _graph_models():
@@ -124,12 +141,8 @@ class StepRunner:
         self.eager_steps = self.replayed_steps = 0
         if self.graph:
             self._check_graph_support()
-        # the fused criteria: nn.MSELoss(reduction='mean') and this package's mpjpe; any other callable is called as it is
-        self.fused_loss = None
-        if isinstance(criterion, nn.MSELoss) and criterion.reduction == "mean":
-            self.fused_loss = ops.pose_mse
-        elif criterion is mpjpe:
-            self.fused_loss = ops.pose_mpjpe
+        # the fused criteria (fused_criterion); any other callable is called as it is
+        self.fused = fused_criterion(criterion)
         self.fused_opt = hasattr(optimizer, "clip_step")
         self.state = None
         if self.graph:
@@ -159,10 +172,10 @@ class StepRunner:
         if not hasattr(self.opt, "clip_step"):
             raise ValueError("StepRunner(graph=True) needs an optimizer with clip_step (posenet_optimizer / optim.PosenetAdam), got %s"
                              % type(self.opt).__name__)
-        c = self.criterion
-        if not ((isinstance(c, nn.MSELoss) and c.reduction == "mean") or c is mpjpe):
-            raise ValueError("StepRunner(graph=True) captures the two fused criteria only: nn.MSELoss(reduction='mean') and this "
-                             "package's utils.loss.mpjpe, got %r" % (c,))
+        if fused_criterion(self.criterion) is None:
+            raise ValueError("StepRunner(graph=True) captures the four fused criteria only: nn.MSELoss(reduction='mean') and this "
+                             "package's utils.loss.mpjpe, utils.loss.n_mpjpe and utils.loss.JointWeightedMpjpe instances, got %r"
+                             % (self.criterion,))
         if self.opt.world_size() > 1:
             raise NotImplementedError("StepRunner(graph=True) with a world size above 1: a captured step cannot hold the gradient "
                                       "all-reduce (segmented graphs around the collective are not implemented)")
@@ -188,14 +201,27 @@ class StepRunner:
         self.eager_steps += 1
         self._body(inputs, targets, meter, num_poses, row[0:1], row[1:2], None)
 
+    def _fused_loss(self, outputs, targets, num_poses, rec, loss_slot):
+        """(loss, grad) of the fused criterion from one launch pair, the meter record updated on the device"""
+        kw = dict(meter=rec, workspace=self.workspace, loss=loss_slot)
+        if self.fused == "mse":
+            return ops.pose_mse(outputs, targets, num_poses, **kw)
+        if self.fused == "mpjpe":
+            return ops.pose_mpjpe(outputs, targets, num_poses, **kw)
+        if self.fused == "n_mpjpe":
+            if outputs.dim() != 4:                # what utils.loss.n_mpjpe raises
+                raise ValueError("n_mpjpe: poses must be (B, F, 16, 3), got %s" % (tuple(outputs.shape),))
+            return ops.pose_nmpjpe(outputs, targets, num_poses, **kw)
+        return ops.pose_wmpjpe(outputs, targets, self.criterion.buffer(outputs.device), num_poses, **kw)
+
     def _body(self, inputs, targets, meter, num_poses, loss_slot, norm_slot, lr_dev):
         rec = None if meter is None else self.meters[METERS.index(meter)]
         outputs = self.model(inputs)
         self.opt.zero_grad()
-        if self.fused_loss is not None:
+        if self.fused is not None:
             if tuple(outputs.shape) != tuple(targets.shape):
                 raise ValueError("posenet output %s and target %s differ in shape" % (tuple(outputs.shape), tuple(targets.shape)))
-            _, grad = self.fused_loss(outputs, targets, num_poses, meter=rec, workspace=self.workspace, loss=loss_slot)
+            _, grad = self._fused_loss(outputs, targets, num_poses, rec, loss_slot)
             outputs.backward(grad.view(outputs.shape))
         else:
             loss = self.criterion(outputs, targets)
@@ -223,8 +249,10 @@ class StepRunner:
                 imm.append((m.momentum, m.eps))
             elif isinstance(m, nn.Dropout):
                 imm.append(m.p)
+        # the weighted criterion's captured launch reads the weight buffer in place: another buffer is another graph
+        crit = (self.fused, self.criterion.buffer(self.device).data_ptr()) if self.fused == "wmpjpe" else self.fused
         return (tuple(inputs.shape), tuple(targets.shape), -1 if meter is None else METERS.index(meter), type(self.model),
-                self.model.precision, "mse" if self.fused_loss is ops.pose_mse else "mpjpe", int(num_poses), tuple(imm))
+                self.model.precision, crit, int(num_poses), tuple(imm))
 
     def _graph_step(self, inputs, targets, meter, num_poses, row):
         st = self.state

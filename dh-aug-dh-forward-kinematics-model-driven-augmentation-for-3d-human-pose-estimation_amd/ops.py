@@ -528,6 +528,86 @@ def pose_mpjpe(pred, target, poses, meter=None, workspace=None, loss=None):
     return loss, grad
 
 
+def _pose_criterion(name, pred, target, poses, meter, workspace, loss):
+    """the checks and outputs pose_nmpjpe and pose_wmpjpe share: (y, x, P, grad, loss, workspace)"""
+    if tuple(pred.shape) != tuple(target.shape):
+        raise ValueError("%s: pred %s and target %s differ in shape" % (name, tuple(pred.shape), tuple(target.shape)))
+    if pred.dim() < 2 or tuple(pred.shape[-2:]) != (16, 3):
+        raise ValueError("%s: poses must be (..., 16, 3), got %s" % (name, tuple(pred.shape)))
+    if int(poses) < 0:
+        raise ValueError("%s: poses must be >= 0" % name)
+    y = _dev(pred.detach(), torch.float32, name)
+    x = _dev(target.detach(), torch.float32, name)
+    dev = y.device
+    if meter is not None:
+        assert meter.is_cuda and meter.dtype == torch.int64 and meter.numel() == _lib.LOSS_METER_WORDS and meter.is_contiguous(), \
+            "%s: meter must be one record of loss_meters()" % name
+    ws = workspace if workspace is not None else posetrain_workspace(dev)
+    grad = torch.empty_like(y)
+    if loss is None:
+        loss = torch.empty(1, dtype=torch.float32, device=dev)
+    assert loss.is_cuda and loss.dtype == torch.float32 and loss.numel() == 1
+    return y, x, y.numel() // 48, grad, loss, ws
+
+
+def pose_nmpjpe(pred, target, poses, meter=None, workspace=None, loss=None):
+    """n_mpjpe forward + backward (dhaug_pose_nmpjpe) over (..., 16, 3) poses, each scaled by its own least-squares scale: returns
+    (loss, grad) with pose_mpjpe's conventions.  `poses` is what the meter counts (the batch size), not the number of (16, 3)
+    poses, which follows from the shape.  An all-zero predicted pose gives a NaN loss and NaN for that pose's gradient."""
+    y, x, P, grad, loss, ws = _pose_criterion("pose_nmpjpe", pred, target, poses, meter, workspace, loss)
+    _lib.call("dhaug_pose_nmpjpe", _p(y), _p(x), P, int(poses), _p(grad), _p(loss), _p(meter), _p(ws), _stream())
+    return loss, grad
+
+
+def wmpjpe_mode(w_shape, joint_shape):
+    """the w_mode of dhaug_pose_wmpjpe from w's shape against pred.shape[:-1]: per pose for (..., 1), per pose and joint for the
+    full shape, shared for (16,) -- the first that fits; None for any other shape"""
+    w_shape, joint_shape = tuple(w_shape), tuple(joint_shape)
+    if w_shape == joint_shape[:-1] + (1,):
+        return _lib.WMPJPE_PER_POSE
+    if w_shape == joint_shape:
+        return _lib.WMPJPE_PER_JOINT
+    if w_shape == (16,):
+        return _lib.WMPJPE_SHARED
+    return None
+
+
+def pose_wmpjpe(pred, target, w, poses, meter=None, workspace=None, loss=None):
+    """mean(w * norm(pred - target, dim=-1)) forward + backward (dhaug_pose_wmpjpe) over (..., 16, 3) poses: returns (loss, grad)
+    with pose_mpjpe's conventions.  w: an fp32 device tensor of shape pred.shape[:-2] + (1,) (one weight per pose),
+    pred.shape[:-1] (per pose and joint) or (16,) (per joint, shared by all poses and read in place); any sign."""
+    name = "pose_wmpjpe"
+    y, x, P, grad, loss, ws = _pose_criterion(name, pred, target, poses, meter, workspace, loss)
+    mode = wmpjpe_mode(w.shape, pred.shape[:-1])
+    if mode is None:
+        raise ValueError("%s: w %s must be %s, %s or (16,)" % (name, tuple(w.shape), tuple(pred.shape[:-2]) + (1,),
+                                                              tuple(pred.shape[:-1])))
+    wd = _dev(w.detach(), torch.float32, name)
+    _lib.call("dhaug_pose_wmpjpe", _p(y), _p(x), P, _p(wd), mode, int(poses), _p(grad), _p(loss), _p(meter), _p(ws), _stream())
+    return loss, grad
+
+
+def pose_byjoint_backward(pred, target, cot):
+    """the backward of mpjpe_byjoint (dhaug_pose_byjoint_backward) for (rows, ..., 3) joints: cot holds one value per entry of
+    pred.shape[1:-1]; returns grad[r, c] = cot[c] (pred - target) / (|pred - target| rows) in pred's shape, 0 at distance 0"""
+    name = "pose_byjoint_backward"
+    if tuple(pred.shape) != tuple(target.shape):
+        raise ValueError("%s: pred %s and target %s differ in shape" % (name, tuple(pred.shape), tuple(target.shape)))
+    if pred.dim() < 2 or pred.shape[-1] != 3:
+        raise ValueError("%s: joints must be (rows, ..., 3), got %s" % (name, tuple(pred.shape)))
+    rows, cols = pred.shape[0], 1
+    for d in pred.shape[1:-1]:
+        cols *= d
+    if cot.numel() != cols:
+        raise ValueError("%s: cot %s must hold one value per column (%d)" % (name, tuple(cot.shape), cols))
+    y = _dev(pred.detach(), torch.float32, name)
+    x = _dev(target.detach(), torch.float32, name)
+    c = _dev(cot.detach(), torch.float32, name)
+    grad = torch.empty_like(y)
+    _lib.call("dhaug_pose_byjoint_backward", _p(y), _p(x), rows, cols, _p(c), _p(grad), _stream())
+    return grad
+
+
 def _flat_f32(t, name, what):
     if t.dim() != 1:
         raise ValueError("%s: %s must be a flat vector, got %s" % (name, what, tuple(t.shape)))

@@ -126,9 +126,10 @@ def compute_AUC(gts, preds, scales=1000, eval_joints=None):
 # mean_velocity_error :180-189, on dhaug_pose_column_errors / dhaug_pose_scaled_errors.  The module's conventions hold: poses
 # are (..., 16, 3), host inputs are uploaded as fp32 and one host read returns the reference's type, device tensors in give
 # device tensors out with no synchronisation.  Every distance, scale and sum is fp64 from the fp32 values; the result is
-# rounded once to the returned type.  The kernels are metrics, not criteria: when `predicted` requires grad (and gradients
-# are enabled) the three torch functions evaluate the reference's expression in plain torch instead, so training code that
-# uses them as a loss keeps working.
+# rounded once to the returned type.  The three torch functions are criteria too: an fp32 device `predicted` that requires
+# grad (gradients enabled, no gradient asked for target or w) goes through an autograd.Function over dhaug_pose_nmpjpe,
+# dhaug_pose_wmpjpe or dhaug_pose_byjoint_backward (first order only); any other `predicted` that requires grad evaluates
+# the reference's expression in plain torch, so training code that uses them as a loss keeps working.
 
 
 def _check_pair(pred, target, name):
@@ -163,6 +164,59 @@ def _wants_grad(predicted):
     return torch.is_tensor(predicted) and predicted.requires_grad and torch.is_grad_enabled()
 
 
+def takes_criterion_kernel(predicted, others=(), within_limits=True):
+    """the rule that sends a call to the fused loss + gradient kernels, from attributes alone: `predicted` is an fp32 device
+    tensor that requires grad, gradients are enabled, no other operand (target, w) requires grad, and the metric kernel's shape
+    limits hold.  Anything else keeps the metric kernel or the plain-torch expression."""
+    return bool(getattr(predicted, "is_cuda", False) and getattr(predicted, "dtype", None) == torch.float32
+                and getattr(predicted, "requires_grad", False) and torch.is_grad_enabled()
+                and not any(getattr(o, "requires_grad", False) for o in others) and within_limits)
+
+
+def _f32_on(t, device):
+    return t.detach().to(device=device, dtype=torch.float32)
+
+
+class _ScalarCriterionFn(torch.autograd.Function):
+    """n_mpjpe / weighted_mpjpe as training criteria, as _MpjpeFn is for mpjpe: ops.pose_nmpjpe (w None) or ops.pose_wmpjpe
+    gives the loss and d loss / d predicted in one launch pair; the gradient is kept for the backward.  First order only."""
+
+    @staticmethod
+    def forward(ctx, predicted, target, w):
+        poses = predicted.numel() // 48
+        if w is None:
+            loss, grad = ops.pose_nmpjpe(predicted, target, poses)
+        else:
+            loss, grad = ops.pose_wmpjpe(predicted, target, w, poses)
+        ctx.save_for_backward(grad)
+        return loss.reshape(())
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_output):
+        (grad,) = ctx.saved_tensors
+        return grad_output * grad, None, None
+
+
+class _ByJointFn(torch.autograd.Function):
+    """mpjpe_byjoint as a training criterion: the value is the metric's (dhaug_pose_column_errors, the same bits), the backward
+    one dhaug_pose_byjoint_backward launch over the saved operands.  First order only."""
+
+    @staticmethod
+    def forward(ctx, predicted, target):
+        sp = tuple(predicted.shape)
+        cols = torch.zeros(_joints(sp[1:]), dtype=torch.float64, device=predicted.device)
+        ops.pose_column_errors(predicted, target, col_sums=cols)
+        ctx.save_for_backward(predicted, target)
+        return (cols / float(sp[0])).reshape(sp[1:-1]).to(torch.float32)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_output):
+        predicted, target = ctx.saved_tensors
+        return ops.pose_byjoint_backward(predicted, target, grad_output), None
+
+
 def _result(v, predicted, host):
     """v (fp64 device tensor) as the torch functions return it: predicted's floating dtype, on the host for host inputs"""
     dtype = predicted.dtype if torch.is_tensor(predicted) else torch.float32
@@ -172,9 +226,12 @@ def _result(v, predicted, host):
 
 def mpjpe_byjoint(predicted, target):
     """the joint error averaged over the FIRST axis only: (N, 16, 3) gives (16,), (B, F, 16, 3) gives (F, 16) -- the shape is
-    predicted.shape[1:-1].  fp64 distances and sums (dhaug_pose_column_errors).  A `predicted` that requires grad is evaluated
-    in plain torch (differentiable), not on the kernel."""
+    predicted.shape[1:-1].  fp64 distances and sums (dhaug_pose_column_errors).  As a criterion (takes_criterion_kernel) the same
+    value with a grad_fn over dhaug_pose_byjoint_backward; any other `predicted` that requires grad -- and the one-pose form,
+    and more than COLERR_MAX_COLS joints per entry -- is evaluated in plain torch (differentiable), not on the kernel."""
     sp = _check_pair(predicted, target, "mpjpe_byjoint")
+    if takes_criterion_kernel(predicted, (target,), len(sp) > 2 and _joints(sp[1:]) <= _lib.COLERR_MAX_COLS):
+        return _ByJointFn.apply(predicted, _f32_on(target, predicted.device))
     if _wants_grad(predicted):
         return torch.mean(torch.norm(predicted - target.to(predicted.device), dim=-1), dim=0)
     if len(sp) == 2:                                  # one pose: the first axis is the joints
@@ -206,10 +263,13 @@ def _weights(w, shape, name):
 def weighted_mpjpe(predicted, target, w):
     """mean(w * norm(predicted - target, dim=-1)) under torch broadcasting of w against predicted.shape[:-1]: one weight per
     joint, per pose ((..., 1)), or any shape that broadcasts to these without enlarging the result; w.shape[0] must be
-    predicted.shape[0].  Weights of any sign.  fp64 distances and sums (dhaug_pose_scaled_errors).  A `predicted` that requires
-    grad is evaluated in plain torch (differentiable), not on the kernel."""
+    predicted.shape[0].  Weights of any sign.  fp64 distances and sums (dhaug_pose_scaled_errors).  As a criterion
+    (takes_criterion_kernel) a 0-d tensor with a grad_fn over dhaug_pose_wmpjpe; any other `predicted` that requires grad is
+    evaluated in plain torch (differentiable), not on the kernel."""
     sp = _check_pair(predicted, target, "weighted_mpjpe")
     w = _weights(w if torch.is_tensor(w) else torch.from_numpy(np.ascontiguousarray(w)), sp[:-1], "weighted_mpjpe")
+    if takes_criterion_kernel(predicted, (target, w)):
+        return _ScalarCriterionFn.apply(predicted, _f32_on(target, predicted.device), _f32_on(w, predicted.device))
     if _wants_grad(predicted):
         return torch.mean(w.to(predicted.device) * torch.norm(predicted - target.to(predicted.device), dim=-1))
     y, x, host = _shaped_pair(predicted, target, "weighted_mpjpe")
@@ -220,11 +280,14 @@ def weighted_mpjpe(predicted, target, w):
 def n_mpjpe(predicted, target):
     """scale-normalised MPJPE of (B, F, 16, 3) poses: per frame s = mean_j(sum target * predicted) / mean_j(sum predicted^2),
     then mpjpe(s * predicted, target).  fp64 scale, distances and sums (dhaug_pose_scaled_errors); an all-zero predicted frame
-    gives NaN, as the reference.  A `predicted` that requires grad is evaluated in plain torch (differentiable), not on the
-    kernel."""
+    gives NaN, as the reference.  As a criterion (takes_criterion_kernel) a 0-d tensor with a grad_fn over dhaug_pose_nmpjpe
+    (a frame the prediction fits exactly up to scale gets a zero gradient); any other `predicted` that requires grad is
+    evaluated in plain torch (differentiable), not on the kernel."""
     if len(tuple(predicted.shape)) != 4:
         raise ValueError("n_mpjpe: poses must be (B, F, 16, 3), got %s" % (tuple(predicted.shape),))
     sp = _check_pair(predicted, target, "n_mpjpe")
+    if takes_criterion_kernel(predicted, (target,)):
+        return _ScalarCriterionFn.apply(predicted, _f32_on(target, predicted.device), None)
     if _wants_grad(predicted):
         target = target.to(predicted.device)
         norm_predicted = torch.mean(torch.sum(predicted ** 2, dim=3, keepdim=True), dim=2, keepdim=True)
@@ -233,6 +296,37 @@ def n_mpjpe(predicted, target):
     y, x, host = _shaped_pair(predicted, target, "n_mpjpe")
     sums = ops.pose_scaled_errors(y, x)
     return _result(sums[0] / float(_joints(sp)), predicted, host)
+
+
+class JointWeightedMpjpe:
+    """weighted_mpjpe with sixteen per-joint weights shared by every pose, as a criterion object: callable (predicted, target).
+    The weights are kept as one fp32 buffer, moved to the device on first use and read there in place by dhaug_pose_wmpjpe
+    (DHAUG_WMPJPE_SHARED) -- StepRunner fuses an instance of this class, and a captured step holds the buffer's address.  A call
+    that takes_criterion_kernel does not send to the kernels (host inputs, fp64, no gradient asked for, ...) is
+    weighted_mpjpe(predicted, target, weights.expand(predicted.shape[:-1])): the same value, evaluated as that function does."""
+
+    def __init__(self, weights):
+        w = torch.as_tensor(weights).detach().to(torch.float32).reshape(-1)
+        if w.numel() != 16:
+            raise ValueError("JointWeightedMpjpe: sixteen weights, one per joint, got %d" % w.numel())
+        self.weights = w.clone().contiguous()
+
+    def buffer(self, device):
+        """the sixteen weights as an fp32 tensor on `device` (moved once; the same tensor from then on)"""
+        d, have = torch.device(device), self.weights.device
+        if have.type != d.type or (d.index is not None and have.index != d.index):
+            self.weights = self.weights.to(d).contiguous()
+        return self.weights
+
+    def __call__(self, predicted, target):
+        sp = _check_pair(predicted, target, "JointWeightedMpjpe")
+        if takes_criterion_kernel(predicted, (target,)):
+            return _ScalarCriterionFn.apply(predicted, _f32_on(target, predicted.device), self.buffer(predicted.device))
+        w = self.buffer(predicted.device) if torch.is_tensor(predicted) and predicted.is_cuda else self.weights
+        return weighted_mpjpe(predicted, target, w.expand(sp[:-1]))
+
+    def __repr__(self):
+        return "JointWeightedMpjpe(%s)" % (self.weights.tolist(),)
 
 
 def mean_velocity_error(predicted, target):

@@ -390,6 +390,48 @@ int dhaug_adam_clip_step_lr(float* param, const float* grad, float* exp_avg, flo
  *   order like dhaug_counter_add: the base of the device dropout stream (dhaug_bn_act_forward_dr) is advanced with it once per step. */
 int dhaug_u64_add(uint64_t* cell, uint64_t value, void* stream);
 
+/* The other criteria of R/utils/loss.py, forward and backward like dhaug_pose_mpjpe (csrc/dhaug_pose_criteria.hip): n_mpjpe
+ * :167-177, weighted_mpjpe :26-32 and the backward of mpjpe_byjoint :17-23.  fp32 in and out; every difference, square, square
+ * root, scale and sum in fp64 from the fp32 values; each gradient element rounded to fp32 once; every element of grad written.
+ *
+ * dhaug_pose_nmpjpe: P poses of (16, 3), two launches.  Per pose, in fp64: pp = sum p.p, tp = sum t.p, s = tp / pp (the
+ *   reference's two means over the joints cancel), r_j = s p_j - t_j, e_j = |r_j|, u_j = r_j / e_j and exactly 0 where e_j == 0,
+ *   a = sum_j u_j.p_j.  With J = 16 P:
+ *     grad_k = fl32((s u_k + a (t_k - 2 s p_k) / pp) / J)   -- torch's autograd of the reference's expression;
+ *     *loss  = fl32(sum of e / J), per-workgroup fp64 partials added in index order by a one-wave second launch.
+ *   Four lanes per pose, each holding four joints in registers; 64 poses per workgroup in a grid-stride loop; the pose's sums meet
+ *   in two-level butterflies over its four lanes: every input element is read once.  pred, tgt, grad: 4-byte aligned; bases on a
+ *   16-byte boundary take the float4 path, others a scalar one with the same values.  A pose whose pp is 0 gives a NaN loss and 48
+ *   NaN gradient values for that pose only, as the reference; a NaN input stays inside its pose's 48 gradient values (and reaches
+ *   the loss).  A pose the prediction fits exactly up to scale (every e_j == 0) gets an all-zero gradient.
+ *   meter (optional, ACCUMULATED into with `poses`, which is the caller's count and need not be P), workspace
+ *   (DHAUG_POSETRAIN_WORKSPACE_BYTES), reproducibility and the one-call-per-workspace rule as dhaug_pose_mse.
+ *   DHAUG_EINVAL: P or poses < 0, NULL grad / loss / workspace, (P > 0) NULL pred / tgt; DHAUG_EUNSUPPORTED: P >= 2^31;
+ *   DHAUG_EALIGN: meter or workspace not 8-byte aligned.  P = 0 is a no-op.
+ *
+ * dhaug_pose_wmpjpe: mean(w |pred - tgt|) of P poses of (16, 3), the same layout, launches, meter, workspace and codes.  w_mode:
+ *     DHAUG_WMPJPE_PER_POSE  (1) one fp32 weight per pose, P values, 4-byte aligned;
+ *     DHAUG_WMPJPE_PER_JOINT (2) one per pose and joint, P x 16 values, 16-byte aligned;
+ *     DHAUG_WMPJPE_SHARED    (3) one per joint shared by all poses, 16 values, 4-byte aligned.
+ *   Weights of any sign.  With d = pred - tgt, e = |d|: grad = fl32(w d / (e J)), exactly 0 where e == 0; *loss = fl32(sum of
+ *   w e / J).  A NaN input gives a NaN loss and a NaN gradient for that joint only.
+ *   DHAUG_EINVAL in addition: NULL w or any other w_mode (checked before P = 0 returns).
+ *
+ * dhaug_pose_byjoint_backward: the backward of mpjpe_byjoint for (rows, cols, 3) joints, one launch.  cot: device fp32[cols], the
+ *   cotangent of the per-column means; grad[r, c] = fl32(cot[c] d / (e rows)), exactly 0 where e == 0.  All pointers 4-byte
+ *   aligned; four joints per lane on 16-byte aligned pred / tgt / grad, a scalar path otherwise and for the rows cols % 4 tail.
+ *   (The forward value is dhaug_pose_column_errors'.)  DHAUG_EINVAL: rows or cols < 0, (rows, cols > 0) a NULL pointer;
+ *   DHAUG_EUNSUPPORTED: rows or cols >= 2^31.  rows = 0 or cols = 0 is a no-op. */
+#define DHAUG_WMPJPE_PER_POSE 1
+#define DHAUG_WMPJPE_PER_JOINT 2
+#define DHAUG_WMPJPE_SHARED 3
+int dhaug_pose_nmpjpe(const float* pred, const float* tgt, int64_t P, int64_t poses, float* grad, float* loss, void* meter,
+                      void* workspace, void* stream);
+int dhaug_pose_wmpjpe(const float* pred, const float* tgt, int64_t P, const float* w, int w_mode, int64_t poses, float* grad,
+                      float* loss, void* meter, void* workspace, void* stream);
+int dhaug_pose_byjoint_backward(const float* pred, const float* tgt, int64_t rows, int64_t cols, const float* cot, float* grad,
+                                void* stream);
+
 /* ------------------------------------------------------------------------------------------------------
  * Dense layers: bf16 MFMA GEMM with fused epilogue
  * ---------------------------------------------------------------------------------------------------- */

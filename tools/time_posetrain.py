@@ -14,14 +14,23 @@ Paths:
 (dhaug_pose_mpjpe: loss, gradient and meter in one launch pair); stock and torch = the generic path, with the reference's torch
 expression mean(norm(predicted - target, dim=-1)) as the criterion (forward + autograd backward).  The paths alternate in one
 process, as for MSE.
+--criterion wmpjpe: fast = utils.loss.JointWeightedMpjpe (dhaug_pose_wmpjpe, sixteen shared weights); stock and torch = the torch
+expression mean(w * norm(predicted - target, dim=-1)) with the weights expanded, on the generic path.
+--criterion n_mpjpe: fast = utils.loss.n_mpjpe (dhaug_pose_nmpjpe); stock and torch = the reference's torch expression.  n_mpjpe
+takes (B, F, 16, 3), so this criterion runs GAN_dataSet_video_mode_train_posenet on clips of ONE frame (batch 1 024 x 1 frame,
+flip on, playback off: the same two steps per batch) with the posenet's output viewed as (B, 1, 16, 3).
 
+  (e) --part e: the three criteria entries alone (ops.pose_nmpjpe, ops.pose_wmpjpe with shared weights: loss + gradient;
+      mpjpe_byjoint: dhaug_pose_column_errors forward + ops.pose_byjoint_backward) against torch's forward + autograd backward of
+      the expressions they replace, at (1 024, 1, 16, 3) and, for the per-joint table, (512, 243, 16, 3).  The two variants
+      alternate call by call in one process; HIP events around each call; per variant the median of five rounds' means.
   (a) per-batch time (two steps) with HIP events around one epoch of --batches batches: >= 20 warm-up steps, five blocks of
       >= 100 timed steps, median of the blocks
   (b) --part k: one epoch only, no warm-up, for  rocprofv3 --kernel-trace --stats --output-format csv -- python tools/time_posetrain.py --part k
       --model M --path P --batches N   (launches per step = the difference of two runs with different N over the steps)
 
-    python tools/time_posetrain.py [--part a|k] [--model stub|wide|both] [--path fast|stock|torch|all] [--batches 50]
-                                   [--criterion mse|mpjpe]"""
+    python tools/time_posetrain.py [--part a|k|e] [--model stub|wide|both] [--path fast|stock|torch|all] [--batches 50]
+                                   [--criterion mse|mpjpe|n_mpjpe|wmpjpe]"""
 import argparse
 import os
 import sys
@@ -36,10 +45,15 @@ import torch.nn as nn
 import dhaug_amd  # noqa: F401
 from dhaug_amd.function_aug import model_pos_train as T
 from dhaug_amd.function_aug.dataloader_update import TensorLoader
+from dhaug_amd import ops
+from dhaug_amd.models_Fk_GAN import video_mode_operate as V
+from dhaug_amd.utils import loss as LS
 from dhaug_amd.utils.loss import mpjpe
+import pose_criteria_util as CU
 import posetrain_util as PU
 
 B = 1024
+CRITERIA = ("mse", "mpjpe", "n_mpjpe", "wmpjpe")
 
 
 class WideMLP(nn.Module):
@@ -51,12 +65,13 @@ class WideMLP(nn.Module):
         self.stem = layer(32)
         self.blocks = nn.ModuleList([nn.Sequential(layer(width), layer(width)) for _ in range(blocks)])
         self.head = nn.Linear(width, 48)
+        self.clips = False                                        # True: the output as (B, 1, 16, 3), what n_mpjpe takes
 
     def forward(self, x):
         y = self.stem(x.reshape(x.shape[0], -1))
         for b in self.blocks:
             y = y + b(y)
-        return self.head(y).view(-1, 16, 3)
+        return self.head(y).view(-1, 1, 16, 3) if self.clips else self.head(y).view(-1, 16, 3)
 
 
 class Wrapped(nn.Module):
@@ -75,29 +90,110 @@ def torch_mpjpe(predicted, target):
     return torch.mean(torch.norm(predicted - target, dim=len(target.shape) - 1))
 
 
-def make(model_name, path):
+def make(model_name, path, clips=False):
     torch.manual_seed(0)
-    model = (PU.StubPosenet() if model_name == "stub" else WideMLP()).cuda()
+    model = (PU.StubPosenet(1 if clips else 0) if model_name == "stub" else WideMLP()).cuda()
+    model.clips = clips
     opt = T.posenet_optimizer(model, 1e-4) if path == "fast" else torch.optim.Adam(model.parameters(), lr=1e-4)
     return model, opt
+
+
+def criteria_of(criterion):
+    """(what the drop-in fuses, a criterion it does not recognise, the plain-torch criterion)"""
+    if criterion == "mse":
+        return nn.MSELoss(reduction="mean"), Wrapped(), nn.MSELoss(reduction="mean")
+    if criterion == "mpjpe":
+        return mpjpe, torch_mpjpe, torch_mpjpe
+    if criterion == "n_mpjpe":
+        return LS.n_mpjpe, CU.torch_n_mpjpe, CU.torch_n_mpjpe
+    w16 = torch.from_numpy(CU.LOOP_W16).cuda()
+    expanded = lambda p, t: CU.torch_weighted_mpjpe(p, t, w16.expand(p.shape[:-1]))
+    return LS.JointWeightedMpjpe(CU.LOOP_W16), expanded, expanded
 
 
 def epoch_fn(model_name, path, nb, criterion="mse"):
     g = torch.Generator(device="cuda").manual_seed(1)
     t3 = torch.randn(nb * B, 16, 3, device="cuda", generator=g)
     i2 = torch.randn(nb * B, 16, 2, device="cuda", generator=g) * 0.4
-    model, opt = make(model_name, path)
+    clips = criterion == "n_mpjpe"
+    model, opt = make(model_name, path, clips)
     args, device = PU.loop_args(), torch.device("cuda")
+    fused, unknown, plain = criteria_of(criterion)
+    if clips:                                                     # clips of one frame through the GAN-clips loop, playback off
+        t3, i2 = t3.view(-1, 1, 16, 3), i2.view(-1, 1, 16, 2)
+        args.GAN_video_playback_input = False
+        pairs = [(t3[i * B:(i + 1) * B], i2[i * B:(i + 1) * B]) for i in range(nb)]
+        as_list = [(None, a, b) for a, b in pairs]
+        if path == "fast":
+            loader = TensorLoader([t3, i2], B)
+            return model, lambda: V.GAN_dataSet_video_mode_train_posenet(model, loader, opt, fused, device, args)
+        if path == "stock":
+            return model, lambda: V.GAN_dataSet_video_mode_train_posenet(model, as_list, opt, unknown, device, args)
+        return model, lambda: PU.stock_loop(model, "gan", pairs, opt, plain, use_flip=True, playback=False)
     as_list = [(t3[i * B:(i + 1) * B], i2[i * B:(i + 1) * B], None, None) for i in range(nb)]
     if path == "fast":
-        loader, crit = TensorLoader([t3, i2], B), (nn.MSELoss(reduction="mean") if criterion == "mse" else mpjpe)
-        return model, lambda: T.train_posenet(model, loader, opt, crit, device, args)
+        loader = TensorLoader([t3, i2], B)
+        return model, lambda: T.train_posenet(model, loader, opt, fused, device, args)
     if path == "stock":
-        crit = Wrapped() if criterion == "mse" else torch_mpjpe
-        return model, lambda: T.train_posenet(model, as_list, opt, crit, device, args)
-    crit = nn.MSELoss(reduction="mean") if criterion == "mse" else torch_mpjpe
+        return model, lambda: T.train_posenet(model, as_list, opt, unknown, device, args)
     pairs = [(a, b) for a, b, _, _ in as_list]
-    return model, lambda: PU.stock_loop(model, "single", pairs, opt, crit, use_flip=True)
+    return model, lambda: PU.stock_loop(model, "single", pairs, opt, plain, use_flip=True)
+
+
+def part_e(rounds=5, reps=50):
+    """the three entries alone against torch's forward + backward of the expressions they replace"""
+    g = torch.Generator(device="cuda").manual_seed(2)
+    w16 = torch.from_numpy(CU.LOOP_W16).cuda()
+
+    def pair(shape):
+        t = torch.randn(shape, device="cuda", generator=g)
+        return (t * 1.1 + 0.3 * torch.randn(shape, device="cuda", generator=g)), t
+
+    def torch_fb(expr, p, t):
+        def run():
+            q = p.detach().requires_grad_(True)
+            v = expr(q, t)
+            (v.sum() if v.dim() else v).backward()
+        return run
+
+    def byjoint_kernels(p, t):
+        cols = torch.zeros(p[0].numel() // 3, dtype=torch.float64, device="cuda")
+        cot = torch.ones(p[0].numel() // 3, device="cuda")
+
+        def run():
+            cols.zero_()
+            ops.pose_column_errors(p, t, col_sums=cols)
+            ops.pose_byjoint_backward(p, t, cot)
+        return run
+
+    small, table = pair((B, 1, 16, 3)), pair((512, 243, 16, 3))
+    ws = ops.posetrain_workspace()
+    cases = [("n_mpjpe (1024, 1, 16, 3)", lambda: ops.pose_nmpjpe(small[0], small[1], B, workspace=ws),
+              torch_fb(CU.torch_n_mpjpe, *small)),
+             ("weighted_mpjpe, 16 shared weights (1024, 1, 16, 3)", lambda: ops.pose_wmpjpe(small[0], small[1], w16, B, workspace=ws),
+              torch_fb(lambda p, t: CU.torch_weighted_mpjpe(p, t, w16.expand(p.shape[:-1])), *small)),
+             ("mpjpe_byjoint (1024, 1, 16, 3)", byjoint_kernels(*small), torch_fb(CU.torch_mpjpe_byjoint, *small)),
+             ("mpjpe_byjoint (512, 243, 16, 3)", byjoint_kernels(*table), torch_fb(CU.torch_mpjpe_byjoint, *table))]
+    for name, ours, theirs in cases:
+        for f in (ours, theirs):                                  # warm-up
+            for _ in range(5):
+                f()
+        means = ([], [])
+        for _ in range(rounds):
+            tot = [0.0, 0.0]
+            for _ in range(reps):
+                for k, f in enumerate((ours, theirs)):            # the variants alternate call by call
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record()
+                    f()
+                    e1.record()
+                    e1.synchronize()
+                    tot[k] += e0.elapsed_time(e1)
+            for k in (0, 1):
+                means[k].append(1e3 * tot[k] / reps)
+        print("entry %-52s kernels %8.1f us  torch forward + backward %8.1f us  (median of %d rounds of %d calls; rounds: %s | %s)"
+              % (name, float(np.median(means[0])), float(np.median(means[1])), rounds, reps,
+                 " ".join("%.1f" % v for v in means[0]), " ".join("%.1f" % v for v in means[1])), flush=True)
 
 
 def part_a(models, paths, nb, criterion):
@@ -125,12 +221,14 @@ def main():
     ap.add_argument("--model", default="both")
     ap.add_argument("--path", default="all")
     ap.add_argument("--batches", type=int, default=50)
-    ap.add_argument("--criterion", choices=("mse", "mpjpe"), default="mse")
+    ap.add_argument("--criterion", choices=CRITERIA, default="mse")
     a = ap.parse_args()
     models = ["stub", "wide"] if a.model == "both" else [a.model]
     paths = ["fast", "stock", "torch"] if a.path == "all" else [a.path]
     T.summary_line = lambda *x, **k: None                        # one line per epoch would drown the report
-    if a.part == "a":
+    if a.part == "e":
+        part_e()
+    elif a.part == "a":
         part_a(models, paths, a.batches, a.criterion)
     else:
         for m in models:
