@@ -947,7 +947,10 @@ int dhaug_mlp_forward_x3(const dhaug_mlp_unit* units, int nunits, int64_t M, voi
     DHAUG_CHECK(ws == nullptr || dhaug_aligned16(ws), DHAUG_EALIGN);
     int img = -1;                                                   /* the virtual buffer whose value the image holds */
     int t16 = -1;                                                   /* which matrix instruction the program's weights are packed for */
-    int stash = -1, stash_map = -1, r1 = -1, r1_map = -1;                 /* ... the register stash (kept for a residual), workspace region 1 (parked) */
+    /* ... the register stash (kept for a residual), workspace region 1 (parked).  Both are written and read back lane by lane, so
+       the adding unit must deal its blocks to the waves exactly as the writing unit did: the same block map AND the same
+       number of slice groups (MAP_1x1 has two: N <= 32 runs one slice on four waves, 33..64 two slices on eight) */
+    int stash = -1, stash_map = -1, r1 = -1, r1_map = -1;
     for (int i = 0; i < nunits; ++i) {
         const dhaug_mlp_unit& s = units[i];
         Unit& u = prog.u[i];
@@ -969,9 +972,9 @@ int dhaug_mlp_forward_x3(const dhaug_mlp_unit* units, int nunits, int64_t M, voi
             DHAUG_CHECK(s.src == img, DHAUG_EUNSUPPORTED);                /* the source must be what the image holds */
             const int chunks = (u.ksteps + 3) / 4;
             DHAUG_CHECK(chunks == 1 || chunks == 2 || chunks == 4, DHAUG_EUNSUPPORTED);
-            const int map = map_of(u.N);
             const int nsl_ = (u.N + 31) / 32;
             const int lg = nsl_ > 4 ? 3 : (nsl_ > 2 ? 2 : (nsl_ == 2 ? 1 : 0));       /* log2(slice groups) */
+            const int map = map_of(u.N) | (lg << 4);                                /* (what stash_map / r1_map compare) */
             int pf = 0;
             if (s.res >= 0) {
                 DHAUG_CHECK(okbuf(s.res) && s.res != s.src, DHAUG_EINVAL);
@@ -1013,8 +1016,14 @@ int dhaug_mlp_forward_x3(const dhaug_mlp_unit* units, int nunits, int64_t M, voi
                         DHAUG_CHECK(stash < 0 || stash == s.dst || !(uses(stash, i) & 2), DHAUG_EUNSUPPORTED);
                         pf |= PF_KEEP;
                         stash = s.dst; stash_map = map;
-                    } else if (stash == s.dst) {
-                        stash = -1;                                           /* (the copy is of the old value) */
+                    } else {
+                        if (stash == s.dst) stash = -1;                       /* (the copy is of the old value) */
+                        if (pf & (PF_ADD_STASH | PF_ADD_R1)) {
+                            /* the adding instantiations always keep (fused_mlp_x3_kernel): this unit's result overwrites the
+                               stash, so nobody may add the old content later */
+                            DHAUG_CHECK(stash < 0 || !(uses(stash, i) & 2), DHAUG_EUNSUPPORTED);
+                            stash = -1;
+                        }
                     }
                     if (r1 == s.dst) r1 = -1;
                     img = s.dst;
@@ -1026,7 +1035,7 @@ int dhaug_mlp_forward_x3(const dhaug_mlp_unit* units, int nunits, int64_t M, voi
                 /* an output that adds a residual reads the workspace through g, which holds the output: not supported */
                 return DHAUG_EUNSUPPORTED;
             }
-            u.plan = (lg << 8) | (map << 12) | (chunks << 16) | (pf << 20);   // bits 0..7: index + 1 of the next GEMM unit (below)
+            u.plan = (lg << 8) | ((map & 15) << 12) | (chunks << 16) | (pf << 20);   // bits 0..7: index + 1 of the next GEMM unit (below)
         } else {
             if (u.kind == U_LOAD_KCS) {
                 DHAUG_CHECK(okbuf(s.dst) && u.g != nullptr && u.ld >= 48, DHAUG_EINVAL);

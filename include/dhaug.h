@@ -821,7 +821,11 @@ int dhaug_mlp_plan(const dhaug_mlp_unit* units, int nunits, int64_t M, int32_t* 
  * registers of the lane that produced it, or the workspace) and returns DHAUG_EUNSUPPORTED otherwise.  A value that a later
  * unit adds as a RESIDUAL stays in registers.  Only a partial sum that is PARKED while another branch of the program uses the
  * image and those registers (a result that is added later and read as a source by nobody) waits in a global workspace (fp32,
- * written and read back by the same lane; only the second half of the buffer is touched).  A program with residuals or a
+ * written and read back by the same lane; only the second half of the buffer is touched).  Both are read back lane by lane,
+ * so the unit that adds a value must deal its blocks to the waves as the unit that wrote it did: n of both in the same one of
+ * 1..32, 33..64, 65..128, 129..256 (DHAUG_EUNSUPPORTED otherwise).  A unit that adds a residual or a parked sum always leaves
+ * its own result in those registers: a kept value that a later unit would add once more is DHAUG_EUNSUPPORTED.
+ * A program with residuals or a
  * parked sum passes g = a 16-byte aligned buffer of DHAUG_MLP_X3_WORKSPACE_BYTES, shared with no concurrent launch, in its
  * GEMM units that are not outputs (any content).
  * Differences from dhaug_mlp_forward: weights come from dhaug_pack_wfrag_f16x2; only LOAD_F32 (cols and ld even, 8-byte

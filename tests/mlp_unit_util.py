@@ -193,10 +193,12 @@ class _State:
         self.bnd[b][:] = 0.0
 
 
-def _exactness(what, x, W, extra):
+def _exactness(what, x, W, extra, fmt=None, fmt_name="bf16"):
     """asserts the condition of the module docstring for pre = x W^T + sum(extra) and returns the bits it needs.  x (M, K),
-    W (N, K), extra: list of (M, N) or (N,) arrays (bias, residual)."""
-    assert is_bf16(x) and is_bf16(W), "%s: an operand is no bf16 value" % what
+    W (N, K), extra: list of (M, N) or (N,) arrays (bias, residual).  fmt: the predicate the operands must satisfy (default:
+    bf16 values; the parity harness, tests/mlp_x3_unit_util.py, passes fp16 pieces)."""
+    fmt = is_bf16 if fmt is None else fmt
+    assert fmt(x) and fmt(W), "%s: an operand is no %s value" % (what, fmt_name)
     S = np.abs(x) @ np.abs(W).T
     nz = W != 0
     nnz = int(nz.sum(1).max()) if W.size else 0
