@@ -12,6 +12,9 @@ _u64 = ctypes.c_uint64
 SIGNATURES = {
     "dhaug_fk_forward": [_vp, _vp, _vp, _vp, _i64, _i32, _vp],
     "dhaug_fk_backward": [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp],
+    "dhaug_fk_jacobian": [_vp, _vp, _vp, _i64, _vp],
+    "dhaug_ik_fit": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _f32, _vp],
+    "dhaug_ik_track": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _f32, _vp],
     "dhaug_gen_tail_forward": [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp],
     "dhaug_gen_tail_forward_critics": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _u64, _u64, _vp, _i64, _i32, _i32, _vp],
     "dhaug_gen_tail_backward": [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp],
@@ -123,6 +126,8 @@ ATTN_MAX_BLOCKS = 8192                                 # DHAUG_ATTN_MAX_BLOCKS
 GELU_MAX_BLOCKS = 2048                                 # DHAUG_GELU_MAX_BLOCKS
 FK_MAX_BLOCKS = 10240                                  # DHAUG_FK_MAX_BLOCKS
 GEN_TAIL4_MAX_BLOCKS = 4096                            # DHAUG_GEN_TAIL4_MAX_BLOCKS
+FK_JACOBIAN_MAX_BLOCKS = 1024                          # DHAUG_FK_JACOBIAN_MAX_BLOCKS
+IK_MAX_BLOCKS = 512                                    # DHAUG_IK_MAX_BLOCKS
 
 
 def layernorm_workspace_doubles(C):

@@ -29,6 +29,21 @@ def pack_angles(right_leg, left_leg, body, right_hand, left_hand, global_rot):
     return torch.cat([right_leg, left_leg, body, right_hand, left_hand, zero, global_rot], dim=1)
 
 
+def unpack_angles(angles37):
+    """(N,37) generator_angle layout -> the reference's keyword arguments: the inverse of pack_angles (slot 33 is dropped).
+    change_3d_joint_angle(**unpack_angles(a), **lengths, root_3d_pos=root) rebuilds the pose the angles stand for."""
+    a = angles37.reshape(-1, 37)
+    return {"right_leg_joints_angle": a[:, 0:5], "left_leg_joints_angle": a[:, 5:10], "body_joints_angle": a[:, 10:23],
+            "right_hand_joints_angle": a[:, 23:28], "left_hand_joints_angle": a[:, 28:33],
+            "generator_global_rot_3d_pos_angle": a[:, 34:37]}
+
+
+def bone_len_kwargs(bone_len):
+    """(N,15) used_16key_15bone_len_table order -> the reference's fifteen *_len keyword arguments"""
+    b = bone_len.reshape(-1, 15)
+    return {k: b[:, i] for i, k in enumerate(_BONE_KW)}
+
+
 class Forward_Kinematics_DH_Model():
     def __init__(self, args, train_subjects, dataset):
         self.args = args
@@ -183,6 +198,60 @@ class Forward_Kinematics_DH_Model():
         pos = ops.fk_forward(t(a37), t(bl), t(np.asarray(self.generator_root)), 32).cpu().numpy().astype(np.float32)
         return pos, self.generator_3d_pos_angle, self.generator_global_rot_3d_pos_angle, self.generator_bone_len, \
             self.generator_root
+
+    # ------------------------------------------------------------------ inverse kinematics (no counterpart in the reference)
+    def ik_limits(self, limits="generator"):
+        """(lo, hi), 37 degrees each: "generator" (the generator's joint limits), "normal" (the 'normal' sampler's table,
+        slots 34..36 from _NORMAL_GLOBAL; slot 23, which the sampler skips, and slot 33 are pinned to 0) or a (lo, hi) pair."""
+        if isinstance(limits, str):
+            if limits == "generator":
+                return list(ops.IK_GENERATOR_LO), list(ops.IK_GENERATOR_HI)
+            if limits == "normal":
+                lo = [0.0 if v is None else float(v) for v in self._NORMAL_LO] + [float(g[0]) for g in self._NORMAL_GLOBAL]
+                hi = [0.0 if v is None else float(v) for v in self._NORMAL_HI] + [float(g[1]) for g in self._NORMAL_GLOBAL]
+                return lo, hi
+            raise ValueError("limits: 'generator', 'normal' or a (lo, hi) pair, got %r" % (limits,))
+        lo, hi = limits
+        return lo, hi
+
+    def _ik_device(self, x):
+        if torch.is_tensor(x):
+            return x
+        if self.device is None:
+            raise RuntimeError("Forward_Kinematics_DH_Model needs a GPU (no CPU fallback exists)")
+        return torch.as_tensor(np.ascontiguousarray(x, dtype=np.float32), device=self.device)
+
+    def fit_pose(self, pose16, init=None, iters=20, limits="generator", clamp_init=False):
+        """Poses (...,16,3) (device tensor or numpy) -> IkFit(angles37, bone_len, root, residual) of device tensors: the DH
+        parameters whose FK reproduces each pose as closely as `iters` damped least-squares steps from `init` (or the
+        T-pose) get inside `limits`.  Judge a fit by `residual` (metres), not by its angles: several slots are redundant."""
+        lo, hi = self.ik_limits(limits)
+        return ops.ik_fit(self._ik_device(pose16), None if init is None else self._ik_device(init), lo, hi, iters=iters,
+                          clamp_init=clamp_init)
+
+    def fit_sequences(self, poses, lengths=None, init=None, iters=8, limits="generator", clamp_init=False):
+        """Tracks sequences frame by frame, each frame started from the one before.  `poses`: a list of (T_s,16,3) arrays
+        (numpy or tensors; concatenated and uploaded once; `lengths` is then taken from them) or one (T,16,3) array with
+        `lengths`, the frames per sequence.  `init` (S,37) starts frame 0 of each sequence.  Returns IkFit over all frames."""
+        if isinstance(poses, (list, tuple)):
+            if lengths is None:
+                lengths = [int(np.shape(q)[0]) for q in poses]
+            if all(torch.is_tensor(q) for q in poses):
+                poses = torch.cat([q.reshape(-1, 16, 3) for q in poses], dim=0)
+            else:
+                poses = np.concatenate([np.asarray(q.cpu() if torch.is_tensor(q) else q, dtype=np.float32).reshape(-1, 16, 3)
+                                        for q in poses], axis=0)
+        if lengths is None:
+            raise ValueError("fit_sequences: lengths are needed when poses is one array")
+        lengths = [int(v) for v in (lengths.tolist() if hasattr(lengths, "tolist") else lengths)]
+        if any(v < 1 for v in lengths):
+            raise ValueError("fit_sequences: every sequence has at least one frame, got %s" % lengths[:8])
+        off = [0]
+        for v in lengths:
+            off.append(off[-1] + v)
+        lo, hi = self.ik_limits(limits)
+        return ops.ik_track(self._ik_device(poses), off, None if init is None else self._ik_device(init), lo, hi, iters=iters,
+                            clamp_init=clamp_init)
 
     def init_Fk_DH_angle(self):
         """T-pose with the default lengths (:824-858)."""

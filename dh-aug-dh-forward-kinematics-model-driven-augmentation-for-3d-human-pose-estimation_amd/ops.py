@@ -71,6 +71,116 @@ def fk_backward(angles, bone_len, grad_out16):
     return ga, gb, gr
 
 
+# ---------------------------------------------------------------------------------------------- IK
+IK_DEAD_SLOTS = (4, 9, 22, 23, 28, 33)          # pinned to 0 by the generator (Fk_generator.py:136)
+# the generator's joint limits per slot, degrees (kAngLo / kAngHi of csrc/dhaug_fk_math.h)
+IK_GENERATOR_LO = [-110, -110, -110, -180, 0, -65, -65, -110, -180, 0] + [-180] * 12 + [0, 0] + \
+                  [-155, -155, -100, 0, 0, -65, -65, -100, 0, 0] + [-180, -180, -180]
+IK_GENERATOR_HI = [65, 65, 180, 0, 0, 110, 110, 180, 0, 0] + [180] * 12 + [0, 0] + \
+                  [65, 65, 180, 180, 0, 155, 155, 180, 180, 0] + [180, 180, 180]
+IkFit = collections.namedtuple("IkFit", "angles37 bone_len root residual")
+
+
+def fk_jacobian(angles, bone_len):
+    """(N,37) deg, (N,15) m -> (N,48,37): d joint coordinate / d angle slot, metres per degree (dhaug_fk_jacobian)."""
+    a = _dev(angles, torch.float32, "fk_jacobian").reshape(-1, 37)
+    b = _dev(bone_len, torch.float32, "fk_jacobian").reshape(-1, 15)
+    N = a.shape[0]
+    if b.shape[0] != N:
+        raise ValueError("fk_jacobian: %d rows of angles, %d of bone lengths" % (N, b.shape[0]))
+    J = torch.empty((N, 48, 37), dtype=torch.float32, device=a.device)
+    _lib.call("dhaug_fk_jacobian", _p(a), _p(b), _p(J), N, _stream())
+    return J
+
+
+def _ik_shape(pose16, name):
+    if not torch.is_tensor(pose16) or pose16.dim() < 2 or tuple(pose16.shape[-2:]) != (16, 3):
+        raise ValueError("%s: poses must be a tensor that views as (..., 16, 3), got %s"
+                         % (name, tuple(pose16.shape) if torch.is_tensor(pose16) else type(pose16).__name__))
+
+
+def _ik_steps(iters, lambda0, name):
+    if int(iters) < 1:
+        raise ValueError("%s: iters must be at least 1, got %r" % (name, iters))
+    if not float(lambda0) > 0.0:
+        raise ValueError("%s: lambda0 must be positive, got %r" % (name, lambda0))
+
+
+def _ik_limits(lo, hi, name):
+    """the limits as two host lists of 37 (lo <= hi checked), and whether they are the caller's"""
+    if lo is None and hi is None:
+        return IK_GENERATOR_LO, IK_GENERATOR_HI, False
+    if lo is None or hi is None:
+        raise ValueError("%s: lo and hi come together" % name)
+    hl = [float(v) for v in (lo.detach().reshape(-1).cpu().tolist() if torch.is_tensor(lo) else list(lo))]
+    hh = [float(v) for v in (hi.detach().reshape(-1).cpu().tolist() if torch.is_tensor(hi) else list(hi))]
+    if len(hl) != 37 or len(hh) != 37:
+        raise ValueError("%s: limits have 37 entries each, got %d and %d" % (name, len(hl), len(hh)))
+    bad = [i for i in range(37) if not hl[i] <= hh[i]]
+    if bad:
+        raise ValueError("%s: lo > hi at slot(s) %s" % (name, bad))
+    return hl, hh, True
+
+
+def _ik_init(init, rows, hl, hh, clamp_init, dev, name):
+    if init is None:
+        return None
+    i = _dev(init, torch.float32, name).reshape(-1, 37)
+    if i.shape[0] != rows:
+        raise ValueError("%s: init has %d rows, expected %d" % (name, i.shape[0], rows))
+    if not clamp_init:
+        lo_t = torch.tensor(hl, dtype=torch.float32, device=dev)
+        hi_t = torch.tensor(hh, dtype=torch.float32, device=dev)
+        if bool(((i < lo_t) | (i > hi_t)).any()):
+            raise ValueError("%s: init lies outside the limits (pass clamp_init=True to clamp it)" % name)
+    return i
+
+
+def _ik_outputs(T, dev):
+    return (torch.empty((T, 37), dtype=torch.float32, device=dev), torch.empty((T, 15), dtype=torch.float32, device=dev),
+            torch.empty((T, 3), dtype=torch.float32, device=dev), torch.empty((T,), dtype=torch.float32, device=dev))
+
+
+def ik_fit(pose16, init=None, lo=None, hi=None, iters=20, lambda0=1e-3, clamp_init=False):
+    """Poses (...,16,3) -> IkFit(angles37 (N,37) deg, bone_len (N,15), root (N,3), residual (N) m): `iters` damped
+    least-squares steps per pose from `init` (N,37) or the T-pose, inside (lo, hi) or the generator's limits (dhaug_ik_fit).
+    ValueError before any launch for a bad shape, lo > hi, iters < 1 or an init outside the limits (unless clamp_init)."""
+    _ik_shape(pose16, "ik_fit")
+    _ik_steps(iters, lambda0, "ik_fit")
+    hl, hh, own = _ik_limits(lo, hi, "ik_fit")
+    p = _dev(pose16, torch.float32, "ik_fit").reshape(-1, 48)
+    N = p.shape[0]
+    lim = torch.tensor([hl, hh], dtype=torch.float32, device=p.device) if own else None
+    i = _ik_init(init, N, hl, hh, clamp_init, p.device, "ik_fit")
+    ang, bl, root, res = _ik_outputs(N, p.device)
+    _lib.call("dhaug_ik_fit", _p(p), _p(i), _p(None if lim is None else lim[0]), _p(None if lim is None else lim[1]), _p(ang),
+              _p(bl), _p(root), _p(res), N, int(iters), float(lambda0), _stream())
+    return IkFit(ang, bl, root, res)
+
+
+def ik_track(pose16, seq_offset, init=None, lo=None, hi=None, iters=8, lambda0=1e-3, clamp_init=False):
+    """Concatenated sequences: pose16 (T,16,3), seq_offset S + 1 ascending frame indices from 0 to T (a host sequence or a
+    tensor; checked on the host).  Frame 0 of sequence s starts from init[s] (S,37) or the T-pose, frame t from frame t - 1's
+    solution (dhaug_ik_track).  Returns IkFit over the T frames."""
+    _ik_shape(pose16, "ik_track")
+    _ik_steps(iters, lambda0, "ik_track")
+    hl, hh, own = _ik_limits(lo, hi, "ik_track")
+    T = pose16.numel() // 48
+    off = [int(v) for v in (seq_offset.detach().reshape(-1).cpu().tolist() if torch.is_tensor(seq_offset) else list(seq_offset))]
+    if len(off) < 1 or off[0] != 0 or off[-1] != T or any(b <= a for a, b in zip(off, off[1:])):
+        raise ValueError("ik_track: seq_offset must increase from 0 to the number of frames (%d), got %s%s"
+                         % (T, off[:8], "..." if len(off) > 8 else ""))
+    S = len(off) - 1
+    p = _dev(pose16, torch.float32, "ik_track").reshape(-1, 48)
+    lim = torch.tensor([hl, hh], dtype=torch.float32, device=p.device) if own else None
+    i = _ik_init(init, S, hl, hh, clamp_init, p.device, "ik_track")
+    off_t = torch.tensor(off, dtype=torch.int64, device=p.device)
+    ang, bl, root, res = _ik_outputs(T, p.device)
+    _lib.call("dhaug_ik_track", _p(p), _p(off_t), _p(i), _p(None if lim is None else lim[0]), _p(None if lim is None else lim[1]),
+              _p(ang), _p(bl), _p(root), _p(res), S, int(iters), float(lambda0), _stream())
+    return IkFit(ang, bl, root, res)
+
+
 def gen_tail_forward(head, bone_len, scaler, use_preangle=True, want_angles=False):
     h = _dev(head, torch.float32, "gen_tail_forward").reshape(-1, 35)
     b = _dev(bone_len, torch.float32, "gen_tail_forward").reshape(-1, 15)

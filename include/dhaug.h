@@ -1223,6 +1223,38 @@ int dhaug_gelu_forward(const float* z, int64_t ld_z, void* y, int y_bf16, int64_
 int dhaug_gelu_backward(const float* z, int64_t ld_z, const void* g, int g_bf16, int64_t ld_g, void* dz, int dz_bf16, int64_t ld_dz,
                         int64_t M, int64_t C, void* stream);
 
+/* ------------------------------------------------------------------------------------------------------
+ * Inverse kinematics of the DH skeleton (csrc/dhaug_ik.hip, csrc/dhaug_ik_math.h).  The reference has no counterpart: it
+ * ships the plots of the dataset's angle distributions (my_draw_original_dataset_distribute_for_paper) but not the solver.
+ * One lane owns one pose (dhaug_ik_track: one sequence); no atomics, the same call gives the same bits; fp32 throughout.
+ *
+ * dhaug_fk_jacobian: J (N,48,37), row 3 j + c = coordinate c of joint j of dhaug_fk_forward(out_joints = 16), column = angle
+ *   slot, metres per degree: d p_j / d theta_k = (pi/180) z_k x (p_j - t_k) for the joints behind k.  It is the Jacobian with
+ *   respect to the generator's 31 live slots: the columns of the six slots the generator pins to 0 (4, 9, 22, 23, 28, 33) are
+ *   exact zeros (of these FK reads 23 and 28, whose value is taken as 0), and so are the columns of 27 and 32, which move
+ *   no joint.  alpha = +-90 deg is taken as exact, as in dhaug_fk_backward.  The whole matrix is written (a fill, then the
+ *   nonzero entries).  At most DHAUG_FK_JACOBIAN_MAX_BLOCKS workgroups of 64 poses; more poses, more trips.
+ * dhaug_ik_fit: per pose, root = joint 0 (bit for bit), bone_len = the 15 joint distances of used_16key_15bone_len_table,
+ *   and the angles by exactly `iters` Levenberg-Marquardt steps on r = FK16(theta, bone_len, root) - pose:
+ *     (H + lambda diag(H) + 1e-8 I) delta = g,  H = J^T J, g = J^T r (Cholesky);  theta' = clamp(theta - delta, lo, hi);
+ *     accepted when sum |r|^2 falls, then lambda *= 0.3, else theta stays and lambda *= 5;  lambda in [1e-9, 1e6].
+ *   pose16 (N,16,3).  init (N,37) or NULL (T-pose) is clamped to the limits; lo / hi (37 each, device) or both
+ *   NULL (the generator's limits).  angles (N,37): the six pinned slots are written as 0.  residual (N): the largest joint distance
+ *   of the returned solution in metres.  DHAUG_EINVAL for iters < 1, lambda0 <= 0, only one of lo / hi.
+ * dhaug_ik_track: the same over S concatenated sequences, frames seq_offset[s] .. seq_offset[s + 1] - 1 (S + 1 ascending int64 on
+ *   the device, seq_offset[0] >= 0; the caller vouches for them: they address pose16 and every output).  Frame 0 of a sequence
+ *   starts from init (S,37) or the T-pose, frame t from frame t - 1's solution; lambda starts at lambda0 in every frame.
+ *   Parallel over sequences, serial inside one.
+ * dhaug_ik_fit / dhaug_ik_track take at most DHAUG_IK_MAX_BLOCKS workgroups (two fit one CU: 69.25 KB of LDS each). */
+#define DHAUG_FK_JACOBIAN_MAX_BLOCKS 1024
+#define DHAUG_IK_MAX_BLOCKS 512
+int dhaug_fk_jacobian(const float* angles, const float* bone_len, float* J, int64_t N, void* stream);
+int dhaug_ik_fit(const float* pose16, const float* init, const float* lo, const float* hi, float* angles, float* bone_len,
+                 float* root, float* residual, int64_t N, int iters, float lambda0, void* stream);
+int dhaug_ik_track(const float* pose16, const int64_t* seq_offset, const float* init, const float* lo, const float* hi,
+                   float* angles, float* bone_len, float* root, float* residual, int64_t S, int iters, float lambda0,
+                   void* stream);
+
 #ifdef __cplusplus
 }
 #endif
