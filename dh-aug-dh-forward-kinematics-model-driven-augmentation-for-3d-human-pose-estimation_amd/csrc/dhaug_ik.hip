@@ -65,6 +65,29 @@ __global__ __launch_bounds__(TILE) void ik_fit_kernel(const float* __restrict__ 
     }
 }
 
+// ik_fit_kernel's layout; the stage table rides in the kernel's arguments (580 B), so a stage's weights are scalar loads
+__global__ __launch_bounds__(TILE) void ik_fit_staged_kernel(const float* __restrict__ pose16, const float* __restrict__ init,
+                                                             const float* __restrict__ lo, const float* __restrict__ hi,
+                                                             const float* __restrict__ bone_len_in, const StageTable st,
+                                                             float* __restrict__ angles, float* __restrict__ bone_len,
+                                                             float* __restrict__ root_out, float* __restrict__ res_out, long long N,
+                                                             float lambda0) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    const int lane = threadIdx.x;
+    Ws ws;
+    ws.p = smem + lane; ws.stride = TILE;
+    const long long ntiles = (N + TILE - 1) / TILE;
+    for (long long tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+        const long long n = tile * TILE + lane;
+        const long long src = n < N ? n : N - 1;               // (idle lanes: as in ik_fit_kernel)
+        V3 root;
+        float ang[37], bl[15], residual;
+        fit_pose_staged(pose16 + src * 48, init != nullptr ? init + src * 37 : nullptr, lo, hi,
+                        bone_len_in != nullptr ? bone_len_in + src * 15 : nullptr, st, lambda0, ws, ang, bl, root, residual);
+        if (n < N) store_fit(n, ang, bl, root, residual, angles, bone_len, root_out, res_out);
+    }
+}
+
 // one lane per sequence: frame t starts from frame t - 1's angles
 __global__ __launch_bounds__(TILE) void ik_track_kernel(const float* __restrict__ pose16, const long long* __restrict__ seq_offset,
                                                         const float* __restrict__ init, const float* __restrict__ lo,
@@ -125,6 +148,19 @@ int dhaug_ik_fit(const float* pose16, const float* init, const float* lo, const 
     if (N == 0) return DHAUG_OK;
     DHAUG_CHECK_PTR(pose16); DHAUG_CHECK_PTR(angles); DHAUG_CHECK_PTR(bone_len); DHAUG_CHECK_PTR(root); DHAUG_CHECK_PTR(residual);
     return launch_ik<ik_fit_kernel>(N, stream, pose16, init, lo, hi, angles, bone_len, root, residual, (long long)N, iters, lambda0);
+}
+
+int dhaug_ik_fit_staged(const float* pose16, const float* init, const float* lo, const float* hi, const float* bone_len_in,
+                        const float* stage_weights, const int* stage_iters, int S, float lambda0, float* angles, float* bone_len,
+                        float* root, float* residual, int64_t N, void* stream) {
+    DHAUG_CHECK(N >= 0 && lambda0 > 0.0f, DHAUG_EINVAL);
+    DHAUG_CHECK((lo == nullptr) == (hi == nullptr), DHAUG_EINVAL);
+    StageTable st;
+    DHAUG_CHECK(make_stage_table(stage_weights, stage_iters, S, st), DHAUG_EINVAL);
+    if (N == 0) return DHAUG_OK;
+    DHAUG_CHECK_PTR(pose16); DHAUG_CHECK_PTR(angles); DHAUG_CHECK_PTR(bone_len); DHAUG_CHECK_PTR(root); DHAUG_CHECK_PTR(residual);
+    return launch_ik<ik_fit_staged_kernel>(N, stream, pose16, init, lo, hi, bone_len_in, st, angles, bone_len, root, residual,
+                                           (long long)N, lambda0);
 }
 
 int dhaug_ik_track(const float* pose16, const int64_t* seq_offset, const float* init, const float* lo, const float* hi,

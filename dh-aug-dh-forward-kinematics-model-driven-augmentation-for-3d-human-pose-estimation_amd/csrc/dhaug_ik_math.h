@@ -205,13 +205,35 @@ struct JacobianStore {
     }
 };
 
+// ---- per-joint weights of the residual: cost = sum_j w_j^2 |r_j|^2, H += w_j^2 c_a . c_b, g += w_j^2 c_a . h (joints 1..15; the
+// root has no term).  A weight table is the same for every pose of a launch, so it never sits in a lane's registers: the
+// device reads the squares from the kernel's arguments (scalar loads) and tests a bit mask for "w_j > 0" (which joints
+// count for the reported residual).
+// UnitWeights is dhaug_ik_fit / dhaug_ik_track: plain sums, nothing skipped.  JointWeights with every square 1.0f gives
+// the same bits (fmaf(1, d, s) = s + d rounded once).
+struct UnitWeights {
+    DHAUG_HD constexpr bool on(int) const { return true; }
+    DHAUG_HD float acc(int, float s, float d) const { return s + d; }
+};
+struct JointWeights {
+    const float* w2;    // 16 squares (entry 0 unused)
+    unsigned mask;      // bit j: w_j > 0
+    DHAUG_HD bool on(int j) const { return (mask >> j) & 1u; }
+    DHAUG_HD float acc(int j, float s, float d) const { return fmaf(w2[j], d, s); }
+};
+
 // Sink of the solver: H += c_a . c_b, g += c_a . (Rg^T r_J).  r_J is taken from the walk's own joint (alpha exact: 4e-8 of a
 // bone length away from fk_pose's, below the rounding of a joint metres from the origin) so that no residual vector has to
-// stay in registers through the walk; the accept / reject test uses fk_pose's cost (residual_cost).
+// stay in registers through the walk; the accept / reject test uses fk_pose's cost (residual_cost).  A joint of weight 0
+// adds exact zeros.  It is NOT branched around: a branch per joint splits the walk into basic blocks, the compiler then
+// contracts a * b - c differently where the product and the difference land in different blocks, and one stage of weights
+// 1 no longer gives fit_pose's bits (seen on gfx950).
+template <class WT>
 struct NormalEquations {
     Ws ws;
     const float* pose;
     V3 root;
+    WT wt;
     template <int JT, int O0, int O1, int NB>
     DHAUG_HD void joint(const V3* c, V3 q, const Rot& Rg) {
         constexpr int n = joint_unknowns<O0, O1, NB>();
@@ -219,9 +241,12 @@ struct NormalEquations {
 #pragma unroll
         for (int a = 0; a < n; ++a) {
             const int ua = joint_unknown<O0, O1, NB>(a);
-            ws(H_FLOATS + ua) += dot(c[a], h);
+            ws(H_FLOATS + ua) = wt.acc(JT, ws(H_FLOATS + ua), dot(c[a], h));
 #pragma unroll
-            for (int b = 0; b <= a; ++b) ws(h_index(ua, joint_unknown<O0, O1, NB>(b))) += dot(c[a], c[b]);
+            for (int b = 0; b <= a; ++b) {
+                const int e = h_index(ua, joint_unknown<O0, O1, NB>(b));
+                ws(e) = wt.acc(JT, ws(e), dot(c[a], c[b]));
+            }
         }
     }
 };
@@ -280,9 +305,11 @@ DHAUG_HD void bone_lengths(const V3* __restrict__ p, float* __restrict__ bl) {
 }
 
 // sum over the joints of |FK16(ang, bl, root)_j - target_j|^2 with the joints as dhaug_fk_forward computes them (Hip = root: no
-// term), and the largest of the 15 terms.  The target is read from the caller's row at every evaluation.
+// term), each term times w_j^2, and the largest |r_j|^2 (unweighted) over the joints of weight > 0.  The target is read from
+// the caller's row at every evaluation.
+template <class WT>
 DHAUG_HD float residual_cost(const float* __restrict__ ang, const float* __restrict__ bl, V3 root, const float* __restrict__ pose,
-                             float& worst) {
+                             const WT& wt, float& worst) {
     V3 p[16];
     fk_pose<true>(ang, bl, p);
     float cost = 0.0f;
@@ -291,8 +318,8 @@ DHAUG_HD float residual_cost(const float* __restrict__ ang, const float* __restr
     for (int j = 1; j < 16; ++j) {
         const V3 r = (p[j] + root) - target_joint(pose, j);
         const float d2 = dot(r, r);
-        cost += d2;
-        worst = fmaxf(worst, d2);
+        cost = wt.acc(j, cost, d2);
+        worst = wt.on(j) ? fmaxf(worst, d2) : worst;
     }
     return cost;
 }
@@ -301,29 +328,41 @@ DHAUG_HD float residual_cost(const float* __restrict__ ang, const float* __restr
 DHAUG_HD float limit_lo(const float* __restrict__ lo, int s) { return lo != nullptr ? lo[s] : kAngLo[s]; }
 DHAUG_HD float limit_hi(const float* __restrict__ hi, int s) { return hi != nullptr ? hi[s] : kAngHi[s]; }
 
-// One pose.  pose: the 48 floats of the target joints; init: 37 start angles or null (T-pose); lo / hi: 37 limits or null
-// (kAngLo / kAngHi).  Writes ang[37] (dead slots 0), bl[15], root, residual (largest joint distance, metres).  Exactly
-// `iters` Levenberg-Marquardt steps, no data-dependent exit.
-DHAUG_HD void fit_pose(const float* __restrict__ pose, const float* __restrict__ init, const float* __restrict__ lo,
-                       const float* __restrict__ hi, int iters, float lambda0, const Ws& ws, float* __restrict__ ang,
-                       float* __restrict__ bl, V3& root, float& residual) {
+// What does not depend on the angles: root = joint 0, the 15 lengths (closed form, or bl_in where the caller has them), and the
+// start clamped into the limits with the dead slots at 0.
+DHAUG_HD void fit_start(const float* __restrict__ pose, const float* __restrict__ init, const float* __restrict__ lo,
+                        const float* __restrict__ hi, const float* __restrict__ bl_in, float* __restrict__ ang,
+                        float* __restrict__ bl, V3& root) {
     {
         V3 tgt[16];
 #pragma unroll
         for (int j = 0; j < 16; ++j) tgt[j] = target_joint(pose, j);
         root = tgt[0];
-        bone_lengths(tgt, bl);
+        if (bl_in == nullptr) {
+            bone_lengths(tgt, bl);
+        } else {
+#pragma unroll
+            for (int i = 0; i < 15; ++i) bl[i] = bl_in[i];
+        }
     }
 #pragma unroll
     for (int s = 0; s < 37; ++s)
         ang[s] = dead_slot(s) ? 0.0f : clampf(init != nullptr ? init[s] : 0.0f, limit_lo(lo, s), limit_hi(hi, s));
-    float lambda = clampf(lambda0, kLamMin, kLamMax), worst;
-    float cost = residual_cost(ang, bl, root, pose, worst);
+}
+
+// `iters` Levenberg-Marquardt steps from ang (in place) under the weights wt, lambda starting at lambda0.  worst: the largest
+// |r_j|^2 of where it ends, over the joints of weight > 0.
+template <class WT>
+DHAUG_HD void lm_steps(const float* __restrict__ pose, const float* __restrict__ lo, const float* __restrict__ hi, int iters,
+                       float lambda0, const Ws& ws, const WT& wt, float* __restrict__ ang, const float* __restrict__ bl, V3 root,
+                       float& worst) {
+    float lambda = clampf(lambda0, kLamMin, kLamMax);
+    float cost = residual_cost(ang, bl, root, pose, wt, worst);
     for (int it = 0; it < iters; ++it) {
         for (int e = 0; e < WS_FLOATS; ++e) ws(e) = 0.0f;
         {
-            NormalEquations ne;
-            ne.ws = ws; ne.pose = pose; ne.root = root;
+            NormalEquations<WT> ne;
+            ne.ws = ws; ne.pose = pose; ne.root = root; ne.wt = wt;
             jacobian_walk(ang, bl, ne);
         }
         factor(ws, lambda);
@@ -336,13 +375,71 @@ DHAUG_HD void fit_pose(const float* __restrict__ pose, const float* __restrict__
             const int s = slot_of(u);
             trial[s] = clampf(ang[s] - ws(H_FLOATS + u), limit_lo(lo, s), limit_hi(hi, s));
         }
-        const float cost2 = residual_cost(trial, bl, root, pose, worst2);
+        const float cost2 = residual_cost(trial, bl, root, pose, wt, worst2);
         const bool accept = cost2 < cost;
 #pragma unroll
         for (int s = 0; s < 37; ++s) ang[s] = accept ? trial[s] : ang[s];
         cost = accept ? cost2 : cost;
         worst = accept ? worst2 : worst;
         lambda = clampf(lambda * (accept ? kLamDown : kLamUp), kLamMin, kLamMax);
+    }
+}
+
+// One pose.  pose: the 48 floats of the target joints; init: 37 start angles or null (T-pose); lo / hi: 37 limits or null
+// (kAngLo / kAngHi).  Writes ang[37] (dead slots 0), bl[15], root, residual (largest joint distance, metres).  Exactly
+// `iters` Levenberg-Marquardt steps, no data-dependent exit.
+DHAUG_HD void fit_pose(const float* __restrict__ pose, const float* __restrict__ init, const float* __restrict__ lo,
+                       const float* __restrict__ hi, int iters, float lambda0, const Ws& ws, float* __restrict__ ang,
+                       float* __restrict__ bl, V3& root, float& residual) {
+    float worst;
+    fit_start(pose, init, lo, hi, nullptr, ang, bl, root);
+    lm_steps(pose, lo, hi, iters, lambda0, ws, UnitWeights(), ang, bl, root, worst);
+    residual = sqrtf(worst);
+}
+
+// ---- coarse to fine: the same steps under one weight table per stage ----
+constexpr int MAX_STAGES = 8;
+// What a staged fit runs, by value: the device takes it as a kernel argument.  w2[s * 16 + j] = w_j^2 of stage s, mask[s] bit j
+// = (w_j > 0), both for joints 1..15 (entry / bit 0 is not read: the root has no term).
+struct StageTable {
+    float w2[MAX_STAGES * 16];
+    int iters[MAX_STAGES];
+    unsigned mask[MAX_STAGES];
+    int stages;
+};
+// Host: fills `t` from S rows of 16 weights and S step counts.  false (t undefined) for S outside 1..MAX_STAGES, a step
+// count below 1, a weight that is negative or not finite, or a last stage without a joint of weight > 0.
+inline bool make_stage_table(const float* weights, const int* iters, int S, StageTable& t) {
+    if (weights == nullptr || iters == nullptr || S < 1 || S > MAX_STAGES) return false;
+    t = StageTable();
+    t.stages = S;
+    for (int s = 0; s < S; ++s) {
+        if (iters[s] < 1) return false;
+        t.iters[s] = iters[s];
+        for (int j = 0; j < 16; ++j) {
+            const float w = weights[s * 16 + j];
+            if (!(w >= 0.0f) || w > 3.0e38f) return false;      // (negative, NaN, inf)
+            if (j == 0) continue;
+            t.w2[s * 16 + j] = w * w;
+            if (!(t.w2[s * 16 + j] <= 3.0e38f)) return false;   // (the square must be finite too)
+            if (w > 0.0f) t.mask[s] |= 1u << j;
+        }
+    }
+    return t.mask[S - 1] != 0;
+}
+
+// One pose, staged.  As fit_pose, but stage s = 0 .. stages - 1 runs iters[s] steps under that stage's weights from where
+// the stage before stopped: lambda back at lambda0, the cost taken anew under the new weights.  bl_in: 15 lengths that
+// replace the closed form, or null.  residual: the largest joint distance over the joints of weight > 0 in the LAST stage.
+DHAUG_HD void fit_pose_staged(const float* __restrict__ pose, const float* __restrict__ init, const float* __restrict__ lo,
+                              const float* __restrict__ hi, const float* __restrict__ bl_in, const StageTable& st, float lambda0,
+                              const Ws& ws, float* __restrict__ ang, float* __restrict__ bl, V3& root, float& residual) {
+    float worst = 0.0f;
+    fit_start(pose, init, lo, hi, bl_in, ang, bl, root);
+    for (int s = 0; s < st.stages; ++s) {
+        JointWeights wt;
+        wt.w2 = st.w2 + s * 16; wt.mask = st.mask[s];
+        lm_steps(pose, lo, hi, st.iters[s], lambda0, ws, wt, ang, bl, root, worst);
     }
     residual = sqrtf(worst);
 }

@@ -221,18 +221,48 @@ class Forward_Kinematics_DH_Model():
             raise RuntimeError("Forward_Kinematics_DH_Model needs a GPU (no CPU fallback exists)")
         return torch.as_tensor(np.ascontiguousarray(x, dtype=np.float32), device=self.device)
 
-    def fit_pose(self, pose16, init=None, iters=20, limits="generator", clamp_init=False):
+    @staticmethod
+    def _ik_schedule(schedule, joint_weights, iters):
+        """(stage_weights, stage_iters) of a staged fit, or None for the plain one"""
+        if schedule is not None and joint_weights is not None:
+            raise ValueError("fit_pose: give a schedule (its stages carry their weights) or joint_weights, not both")
+        if schedule is None:
+            return None if joint_weights is None else ([joint_weights], [iters])
+        if isinstance(schedule, str):
+            if schedule != "coarse_to_fine":
+                raise ValueError("schedule: 'coarse_to_fine' or a list of (weights16, iters) pairs, got %r" % (schedule,))
+            schedule = ops.IK_COARSE_TO_FINE
+        try:
+            stages = [(w, n) for w, n in schedule]
+        except (TypeError, ValueError):
+            raise ValueError("schedule: 'coarse_to_fine' or a list of (weights16, iters) pairs")
+        return [w for w, _ in stages], [n for _, n in stages]
+
+    def fit_pose(self, pose16, init=None, iters=20, limits="generator", clamp_init=False, schedule=None, joint_weights=None,
+                 bone_len=None):
         """Poses (...,16,3) (device tensor or numpy) -> IkFit(angles37, bone_len, root, residual) of device tensors: the DH
         parameters whose FK reproduces each pose as closely as `iters` damped least-squares steps from `init` (or the
-        T-pose) get inside `limits`.  Judge a fit by `residual` (metres), not by its angles: several slots are redundant."""
+        T-pose) get inside `limits`.  Judge a fit by `residual` (metres), not by its angles: several slots are redundant.
+        Without a neighbouring solution to start from, pass schedule="coarse_to_fine" (ops.IK_COARSE_TO_FINE: trunk first, 40
+        steps in all; `iters` is then not used) or a list of (weights16, iters) stages.  joint_weights (16, >= 0) alone is one
+        stage of `iters` steps with the residual of joint j times w_j: 0 for an occluded joint, small for an unsure one -- and
+        then give bone_len (N,15), or the bad joint sets its bones' lengths."""
         lo, hi = self.ik_limits(limits)
-        return ops.ik_fit(self._ik_device(pose16), None if init is None else self._ik_device(init), lo, hi, iters=iters,
-                          clamp_init=clamp_init)
+        staged = self._ik_schedule(schedule, joint_weights, iters)
+        p, i = self._ik_device(pose16), None if init is None else self._ik_device(init)
+        if staged is None:
+            if bone_len is not None:
+                raise ValueError("fit_pose: bone_len goes with a schedule or joint_weights")
+            return ops.ik_fit(p, i, lo, hi, iters=iters, clamp_init=clamp_init)
+        return ops.ik_fit_staged(p, staged[0], staged[1], i, lo, hi, None if bone_len is None else self._ik_device(bone_len),
+                                 clamp_init=clamp_init)
 
-    def fit_sequences(self, poses, lengths=None, init=None, iters=8, limits="generator", clamp_init=False):
+    def fit_sequences(self, poses, lengths=None, init=None, iters=8, limits="generator", clamp_init=False, cold_start=False):
         """Tracks sequences frame by frame, each frame started from the one before.  `poses`: a list of (T_s,16,3) arrays
         (numpy or tensors; concatenated and uploaded once; `lengths` is then taken from them) or one (T,16,3) array with
-        `lengths`, the frames per sequence.  `init` (S,37) starts frame 0 of each sequence.  Returns IkFit over all frames."""
+        `lengths`, the frames per sequence.  `init` (S,37) starts frame 0 of each sequence; without one, cold_start=True fits
+        frame 0 of every sequence by the coarse-to-fine schedule (one batched call) and starts the tracking from that, where
+        the default starts from the T-pose.  Returns IkFit over all frames."""
         if isinstance(poses, (list, tuple)):
             if lengths is None:
                 lengths = [int(np.shape(q)[0]) for q in poses]
@@ -250,8 +280,15 @@ class Forward_Kinematics_DH_Model():
         for v in lengths:
             off.append(off[-1] + v)
         lo, hi = self.ik_limits(limits)
-        return ops.ik_track(self._ik_device(poses), off, None if init is None else self._ik_device(init), lo, hi, iters=iters,
-                            clamp_init=clamp_init)
+        p = self._ik_device(poses)
+        i = None if init is None else self._ik_device(init)
+        if cold_start and i is None:
+            ops._ik_shape(p, "fit_sequences")
+            if p.numel() // 48 != off[-1]:
+                raise ValueError("fit_sequences: lengths add up to %d frames, poses has %d" % (off[-1], p.numel() // 48))
+            first = p.reshape(-1, 16, 3)[torch.as_tensor(off[:-1], device=p.device)]
+            i = ops.ik_fit_staged(first, *zip(*ops.IK_COARSE_TO_FINE), lo=lo, hi=hi).angles37
+        return ops.ik_track(p, off, i, lo, hi, iters=iters, clamp_init=clamp_init)
 
     def init_Fk_DH_angle(self):
         """T-pose with the default lengths (:824-858)."""

@@ -158,6 +158,78 @@ def ik_fit(pose16, init=None, lo=None, hi=None, iters=20, lambda0=1e-3, clamp_in
     return IkFit(ang, bl, root, res)
 
 
+IK_MAX_STAGES = 8                                # MAX_STAGES of csrc/dhaug_ik_math.h
+
+
+def _joint_row(joints):
+    return [1.0 if j in joints else 0.0 for j in range(16)]
+
+
+# Coarse to fine, trunk outwards, 40 steps in all: hips and spine | + thorax, shoulders | + neck, knees, elbows | every joint.
+# (weights16, iters) per stage; entry 0 of a row (the root, which has no residual) is not used.
+IK_COARSE_TO_FINE = (
+    (_joint_row({1, 4, 7}), 8),
+    (_joint_row({1, 4, 7, 8, 10, 13}), 8),
+    (_joint_row({1, 4, 7, 8, 10, 13, 9, 2, 5, 11, 14}), 8),
+    (_joint_row(set(range(16))), 16),
+)
+
+
+def _ik_stages(stage_weights, stage_iters, name):
+    """the schedule as a flat host list of S * 16 weights and a list of S step counts, checked as dhaug_ik_fit_staged checks it"""
+    if torch.is_tensor(stage_weights):
+        stage_weights = stage_weights.detach().cpu().tolist()
+    if torch.is_tensor(stage_iters):
+        stage_iters = stage_iters.detach().cpu().tolist()
+    try:
+        rows = [[float(v) for v in (r.detach().reshape(-1).cpu().tolist() if torch.is_tensor(r) else list(r))] for r in stage_weights]
+        its = [int(v) for v in stage_iters]
+    except TypeError:
+        raise ValueError("%s: stage_weights is a sequence of rows of 16 weights, stage_iters a sequence of step counts" % name)
+    S = len(rows)
+    if not 1 <= S <= IK_MAX_STAGES:
+        raise ValueError("%s: between 1 and %d stages, got %d" % (name, IK_MAX_STAGES, S))
+    if len(its) != S:
+        raise ValueError("%s: %d rows of weights, %d step counts" % (name, S, len(its)))
+    if any(len(r) != 16 for r in rows):
+        raise ValueError("%s: a stage has 16 weights (one per joint), got %s" % (name, [len(r) for r in rows]))
+    if any(v < 1 for v in its):
+        raise ValueError("%s: every stage runs at least 1 step, got %s" % (name, its))
+    f32max = 3.4028234663852886e38
+    if any(not (0.0 <= w and w * w <= f32max) for r in rows for w in r):
+        raise ValueError("%s: weights are finite and not negative (their squares finite in fp32)" % name)
+    if not any(w > 0.0 for w in rows[-1][1:]):
+        raise ValueError("%s: the last stage needs a joint of weight above 0 (joints 1..15)" % name)
+    return [w for r in rows for w in r], its
+
+
+def ik_fit_staged(pose16, stage_weights, stage_iters, init=None, lo=None, hi=None, bone_len=None, lambda0=1e-3, clamp_init=False):
+    """ik_fit in stages, each under a weight per joint on the residual (dhaug_ik_fit_staged): stage_weights S rows of 16 (w_j >= 0;
+    0 leaves the joint out), stage_iters S step counts, S <= 8; a stage starts where the one before stopped, lambda back at
+    lambda0.  bone_len (N,15) replaces the closed-form lengths (give it when a joint of weight 0 may be wrong).  `residual` is
+    the largest distance over the joints of weight > 0 in the last stage.  ops.IK_COARSE_TO_FINE is the schedule for a start
+    from the T-pose: ik_fit_staged(pose, *zip(*IK_COARSE_TO_FINE))."""
+    _ik_shape(pose16, "ik_fit_staged")
+    _ik_steps(1, lambda0, "ik_fit_staged")
+    flat, its = _ik_stages(stage_weights, stage_iters, "ik_fit_staged")
+    hl, hh, own = _ik_limits(lo, hi, "ik_fit_staged")
+    p = _dev(pose16, torch.float32, "ik_fit_staged").reshape(-1, 48)
+    N = p.shape[0]
+    b = None
+    if bone_len is not None:
+        b = _dev(bone_len, torch.float32, "ik_fit_staged").reshape(-1, 15)
+        if b.shape[0] != N:
+            raise ValueError("ik_fit_staged: bone_len has %d rows, expected %d" % (b.shape[0], N))
+    lim = torch.tensor([hl, hh], dtype=torch.float32, device=p.device) if own else None
+    i = _ik_init(init, N, hl, hh, clamp_init, p.device, "ik_fit_staged")
+    ang, bl, root, res = _ik_outputs(N, p.device)
+    S = len(its)
+    _lib.call("dhaug_ik_fit_staged", _p(p), _p(i), _p(None if lim is None else lim[0]), _p(None if lim is None else lim[1]), _p(b),
+              (ctypes.c_float * (S * 16))(*flat), (ctypes.c_int * S)(*its), S, float(lambda0), _p(ang), _p(bl), _p(root), _p(res), N,
+              _stream())
+    return IkFit(ang, bl, root, res)
+
+
 def ik_track(pose16, seq_offset, init=None, lo=None, hi=None, iters=8, lambda0=1e-3, clamp_init=False):
     """Concatenated sequences: pose16 (T,16,3), seq_offset S + 1 ascending frame indices from 0 to T (a host sequence or a
     tensor; checked on the host).  Frame 0 of sequence s starts from init[s] (S,37) or the T-pose, frame t from frame t - 1's

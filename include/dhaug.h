@@ -1245,12 +1245,26 @@ int dhaug_gelu_backward(const float* z, int64_t ld_z, const void* g, int g_bf16,
  *   the device, seq_offset[0] >= 0; the caller vouches for them: they address pose16 and every output).  Frame 0 of a sequence
  *   starts from init (S,37) or the T-pose, frame t from frame t - 1's solution; lambda starts at lambda0 in every frame.
  *   Parallel over sequences, serial inside one.
- * dhaug_ik_fit / dhaug_ik_track take at most DHAUG_IK_MAX_BLOCKS workgroups (two fit one CU: 69.25 KB of LDS each). */
+ * dhaug_ik_fit_staged: dhaug_ik_fit in S stages (coarse to fine), each under a per-joint weight w_j >= 0 on the residual:
+ *     cost = sum_j w_j^2 |r_j|^2,  H = sum_j w_j^2 J_j^T J_j,  g = sum_j w_j^2 J_j^T r_j   (joints 1..15; the root has no term).
+ *   stage_weights (S x 16, HOST, entry 0 of a row is checked but unused) and stage_iters (S, HOST) are read before the call
+ *   returns and travel as kernel arguments: one table for the whole launch.  Stage s starts from where stage s - 1 stopped, with
+ *   lambda back at lambda0 and the cost taken anew under its own weights, and runs exactly stage_iters[s] steps.  A joint of
+ *   weight 0 adds exact zeros (its target must still be a finite number: 0 x NaN is NaN); an unknown that moves only such joints keeps its (clamped) start value bit for bit.  bone_len_in (N,15)
+ *   replaces the closed-form lengths (a joint of weight 0 may be anywhere: it would spoil them), NULL = closed form.  residual:
+ *   the largest joint distance over the joints of weight > 0 in the LAST stage.  One stage of weights 1.0 gives dhaug_ik_fit's
+ *   bits.  DHAUG_EINVAL before any launch for S outside 1..8, a stage_iters below 1, a negative or non-finite weight (or square),
+ *   a last stage whose weights are all 0, lambda0 <= 0, only one of lo / hi.
+ * dhaug_ik_fit / dhaug_ik_fit_staged / dhaug_ik_track take at most DHAUG_IK_MAX_BLOCKS workgroups (two fit one CU: 69.25 KB of
+ *   LDS each). */
 #define DHAUG_FK_JACOBIAN_MAX_BLOCKS 1024
 #define DHAUG_IK_MAX_BLOCKS 512
 int dhaug_fk_jacobian(const float* angles, const float* bone_len, float* J, int64_t N, void* stream);
 int dhaug_ik_fit(const float* pose16, const float* init, const float* lo, const float* hi, float* angles, float* bone_len,
                  float* root, float* residual, int64_t N, int iters, float lambda0, void* stream);
+int dhaug_ik_fit_staged(const float* pose16, const float* init, const float* lo, const float* hi, const float* bone_len_in,
+                        const float* stage_weights, const int* stage_iters, int S, float lambda0, float* angles, float* bone_len,
+                        float* root, float* residual, int64_t N, void* stream);
 int dhaug_ik_track(const float* pose16, const int64_t* seq_offset, const float* init, const float* lo, const float* hi,
                    float* angles, float* bone_len, float* root, float* residual, int64_t S, int iters, float lambda0,
                    void* stream);
