@@ -191,10 +191,12 @@ def _raw_linear(x, W, bias, res, act, slope, prec, out_f32, out=None):
             if F16X3_PLANES:
                 # the split left out of the chain of layers: a layer whose result is wide enough to be the next layer's operand writes the
                 # result's two pieces [hi | lo] from its epilogue (piece width: the next power of two -- 1 024 at DenseDim 1000) and hangs
-                # them on the tensor it returns; the next layer finds them there (a tensor made any other way has none and is split as before)
+                # them on the tensor it returns, with the tensor's version; the next layer finds them there (a tensor made any other way has
+                # none and is split as before, and so is one written in place since -- mul_, clamp_, a write through a view: its version
+                # has moved on and the planes hold the old values)
                 kp2 = _pow2_width(K)
-                have = getattr(x, "_dhaug_f16_planes", None)
-                if have is not None and (have.shape[1] != 2 * kp2 or have.shape[0] != xf.shape[0]):
+                have, version = getattr(x, "_dhaug_f16_planes", None) or (None, None)
+                if have is not None and (version != x._version or have.shape[1] != 2 * kp2 or have.shape[0] != xf.shape[0]):
                     have = None
                 emit = _pow2_width(N) if (N >= 64 and out is None) else 0       # (out: a block of a concatenation -- its consumer splits the whole)
                 if have is not None:
@@ -204,7 +206,7 @@ def _raw_linear(x, W, bias, res, act, slope, prec, out_f32, out=None):
                     r = ops.gemm_nt_f16x3_planes(ops.split_f16(xf, 0, Kp), _w_nt(W, Kp, prec), N, Kp, False, bias=bias, res_f32=rf, act=act,
                                                  slope=slope, planes_kp=emit, out=out)
                 if emit:
-                    r[0]._dhaug_f16_planes = r[1]
+                    r[0]._dhaug_f16_planes = (r[1], r[0]._version)
                     return r[0]
                 return r
             return ops.gemm_nt_f16x3(ops.split_f16(xf, 0, Kp), _w_nt(W, Kp, prec), N, 3 * Kp, bias=bias, res_f32=rf, act=act, slope=slope)

@@ -2038,6 +2038,8 @@ int dhaug_gemm_f16x3_planes(const uint16_t* A, int64_t lda, int a_planes, const 
                             int64_t planes_kp, int64_t M, int64_t N, int64_t kp, int act, float slope, void* stream) {
     DHAUG_CHECK(M >= 0 && N >= 1 && kp >= 16 && kp % 8 == 0, DHAUG_EINVAL);
     DHAUG_CHECK(act >= DHAUG_ACT_NONE && act <= DHAUG_ACT_LRELU, DHAUG_EINVAL);
+    // (the widths and pitches of the result's planes are judged for an empty batch too: any multiple of eight >= N, no power of two asked)
+    if (c_planes != nullptr) DHAUG_CHECK(planes_kp >= N && planes_kp % 8 == 0 && ld_planes >= 2 * planes_kp && ld_planes % 8 == 0, DHAUG_EALIGN);
     if (M == 0) return DHAUG_OK;
     DHAUG_CHECK_PTR(A); DHAUG_CHECK_PTR(B); DHAUG_CHECK_PTR(c_f32);
     int lg = 0;
@@ -2050,8 +2052,12 @@ int dhaug_gemm_f16x3_planes(const uint16_t* A, int64_t lda, int a_planes, const 
                nullptr, 0, 1.0f, nullptr, nullptr, 0};
     if (a_planes) { p.xp_lg = lg + 1; p.xp_map = 0x10u; p.xp_kp = kp; }        // dhaug_split_f16 mode 0 is [hi | hi | lo] = pieces 0 0 1
     if (c_planes != nullptr) {
-        DHAUG_CHECK(planes_kp >= N && planes_kp % 8 == 0 && ld_planes >= 2 * planes_kp && ld_planes % 8 == 0 && dhaug_aligned16(c_planes), DHAUG_EALIGN);
+        DHAUG_CHECK(dhaug_aligned16(c_planes), DHAUG_EALIGN);
         p.cp = c_planes; p.ldcp = ld_planes; p.cp_kp = planes_kp;
+        // the column tiles cover the planes' pad as well: a piece width beyond the last tile of N (N = 600 in pieces of 1 024: three tiles
+        // of N, four of the pieces) would leave columns the next layer contracts over unwritten.  A tile wholly in the pad reads the last
+        // weight row (n0r in p8_body) and stores nothing but the pad's zeros (col_in is false there, and col_pad needs a bf16 output).
+        p.W = planes_kp;
     }
     DHAUG_CHECK(dhaug_p8_supported(p), DHAUG_EUNSUPPORTED);
     return dhaug_p8_launch_f16((hipStream_t)stream, p);

@@ -388,8 +388,8 @@ __device__ __forceinline__ void p8_body(const GemmArgs& p, long long mb, long lo
     s.tail = (p.K % P_BK) != 0;
     s.xp_lg = p.xp_lg; s.xp_map = p.xp_map; s.xp_kp = p.xp_kp;
     s.sm = (lds_addr)p8sm;
-    // (a column tile that lies wholly in the zero-pad columns [N, n_pad) has no weight row of its own: it reads the last one and
-    // stores zeros)
+    // (a column tile that lies wholly in the zero-pad columns [N, n_pad) -- or in the pad [N, cp_kp) of the result's planes -- has no
+    // weight row of its own: it reads the last one and stores zeros)
     const long long n0r = n0 < p.N ? n0 : p.N - 1;
     s.baseA = p.A + m0 * p.lda;
     s.baseB = p.B + n0r * p.ldb;

@@ -680,7 +680,10 @@ int dhaug_gemm_f16x3(const uint16_t* A, int64_t lda, const uint16_t* B, int64_t 
  * columns each (a_planes != 0: A = dhaug_split_f16(x, mode 2), lda >= 2 kp, kp = 64 * 2^j -- DenseDim 1000 is padded to 1 024 --; the
  * kernel reads piece (0 0 1)[s] for K-segment s of B = dhaug_split_f16(W, mode 1, pad kp); a_planes == 0: A is the mode 0 operand,
  * lda >= 3 kp, any kp), and the result may be written once more as such pieces (c_planes, optional: planes_kp >= N columns per piece,
- * ld_planes >= 2 planes_kp, columns [N, planes_kp) zero) -- bit for bit dhaug_split_f16(c_f32, mode 2, pad planes_kp), from the
+ * any multiple of 8 -- no power of two is asked of the producer, only of the layer that takes the pieces as its a_planes operand --,
+ * ld_planes >= 2 planes_kp and % 8 == 0, columns [N, planes_kp) of both pieces zero for EVERY such planes_kp: the launch covers
+ * max(N, planes_kp) columns with tiles, so a pad that reaches beyond the last 256-column tile of N is written too; columns beyond
+ * 2 planes_kp of a wider row are left alone) -- bit for bit dhaug_split_f16(c_f32, mode 2, pad planes_kp), from the
  * epilogue's registers: the next layer's operand without a split launch (4 instead of 6 bytes per value, read and written once).
  * Same product terms in the same order as dhaug_gemm_f16x3 on the mode 0 operand of the same padded width: identical results.
  * DHAUG_EUNSUPPORTED where the ping-pong kernel does not take the shape. */

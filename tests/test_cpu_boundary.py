@@ -153,6 +153,13 @@ def test_argument_errors_are_returned_not_thrown(built):
     assert L.dhaug_gemm_bf16x6_planes(a16, 768, a16, 1536, None, None, 0, None, 0, 0, 0.0, a16, 256, None, 0, 0, 256, 256, 0, 0, 0.0, None) == 0       # empty batch
     assert L.dhaug_gemm_f16x3_planes(a16, 512, 1, a16, 768, None, None, 0, a16, 256, None, 0, 0, 4, 256, 200, 0, 0.0, None) == -3                        # planes need 64 * 2^j
     assert L.dhaug_gemm_f16x3_planes(a16, 512, 1, a16, 768, None, None, 0, a16, 256, a16, 256, 256, 4, 256, 256, 0, 0.0, None) == -2                     # ld_planes < 2 planes_kp
+    assert L.dhaug_gemm_f16x3_planes(a16, 512, 1, a16, 768, None, None, 0, a16, 256, a16, 512, 248, 4, 256, 256, 0, 0.0, None) == -2                     # planes_kp < N
+    assert L.dhaug_gemm_f16x3_planes(a16, 512, 1, a16, 768, None, None, 0, a16, 256, a16, 528, 260, 4, 256, 256, 0, 0.0, None) == -2                     # planes_kp % 8 != 0
+    assert L.dhaug_gemm_f16x3_planes(a16, 512, 1, a16, 768, None, None, 0, a16, 256, a16, 516, 256, 4, 256, 256, 0, 0.0, None) == -2                     # ld_planes % 8 != 0
+    assert L.dhaug_gemm_f16x3_planes(a16, 192, 1, a16, 288, None, None, 0, a16, 256, a16, 512, 256, 4, 256, 96, 0, 0.0, None) == -3                      # a_planes with kp = 96: not 64 * 2^j
+    # a piece width that is no power of two passes the checks (an empty batch: the widths are judged, nothing is launched) ...
+    assert L.dhaug_gemm_f16x3_planes(a16, 512, 1, a16, 768, None, None, 0, a16, 520, a16, 1552, 776, 0, 520, 256, 0, 0.0, None) == 0
+    assert L.dhaug_gemm_f16x3_planes(a16, 512, 1, a16, 768, None, None, 0, a16, 520, a16, 1552, 512, 0, 520, 256, 0, 0.0, None) == -2                    # ... where planes_kp < N does not
     assert L.dhaug_split_bf16(a16, 64, a16, 4, 64, 64, 2, 3, None) == -1                                                                                # mode 2 is a six-term layout
     lay = (dhaug_amd._lib.TnLayer * 1)()
     lay[0].A, lay[0].lda, lay[0].B, lay[0].ldb = a16.value, 64, a16.value, 64
