@@ -114,6 +114,9 @@ SIGNATURES = {
     "dhaug_attn_backward": [_vp, _i32, _i64, _vp, _i32, _i64, _vp, _vp, _i32, _i64, _vp, _i32, _i64, _i64, _i32, _i32, _i32, _f32, _vp],
     "dhaug_gelu_forward": [_vp, _i64, _vp, _i32, _i64, _i64, _i64, _vp],
     "dhaug_gelu_backward": [_vp, _i64, _vp, _i32, _i64, _vp, _i32, _i64, _i64, _i64, _vp],
+    "dhaug_dof_record_layout": [_i64, ctypes.POINTER(_i64)],
+    "dhaug_dof_histogram": [_vp, _i64, _i64, _i64, _vp, _f32, _vp, _vp, _f32, _vp, _vp, _vp],
+    "dhaug_dof_pair_histogram": [_vp, _i64, _i64, _i64, _vp, _f32, ctypes.POINTER(_i32), _i32, _vp, _vp],
 }
 BN_MAX_CHUNKS = 32                                     # DHAUG_BN_MAX_CHUNKS of include/dhaug.h
 GRAPH_MAX_PAIRS = 256                                  # DHAUG_GRAPH_MAX_PAIRS
@@ -129,6 +132,37 @@ FK_MAX_BLOCKS = 10240                                  # DHAUG_FK_MAX_BLOCKS
 GEN_TAIL4_MAX_BLOCKS = 4096                            # DHAUG_GEN_TAIL4_MAX_BLOCKS
 FK_JACOBIAN_MAX_BLOCKS = 1024                          # DHAUG_FK_JACOBIAN_MAX_BLOCKS
 IK_MAX_BLOCKS = 512                                    # DHAUG_IK_MAX_BLOCKS
+DOF_BINS = 361                                         # DHAUG_DOF_BINS
+DOF_MAX_SLOTS = 64                                     # DHAUG_DOF_MAX_SLOTS
+DOF_MAX_PAIRS = 4                                      # DHAUG_DOF_MAX_PAIRS
+DOF_BLOCK = 256                                        # DHAUG_DOF_BLOCK
+DOF_MAX_BLOCKS = 512                                   # DHAUG_DOF_MAX_BLOCKS
+DOF_MIN_STEPS = 16                                     # DHAUG_DOF_MIN_STEPS
+DOF_WORKSPACE_BYTES = DOF_MAX_BLOCKS * 4 * DOF_MAX_SLOTS * 8
+
+
+def dof_record_offsets(D):
+    """DHAUG_DOF_OFF_*(D): the first 8-byte word of every field of a dhaug_dof_histogram record, and its size as 'words'"""
+    return dict(rows=0, skipped=1, nan=2, outside=2 + D, at_lo=2 + 2 * D, at_hi=2 + 3 * D, inf=2 + 4 * D, min=2 + 5 * D,
+                max=2 + 6 * D, sum=2 + 7 * D, sumsq=2 + 8 * D, counts=2 + 9 * D, words=2 + 9 * D + D * DOF_BINS)
+
+
+def dof_record_layout(D):
+    """the same dictionary as dof_record_offsets(D), asked of the loaded library (dhaug_dof_record_layout)"""
+    w = (_i64 * 13)()
+    check(lib().dhaug_dof_record_layout(D, w), "dhaug_dof_record_layout")
+    names = ("rows", "skipped", "nan", "outside", "at_lo", "at_hi", "inf", "min", "max", "sum", "sumsq", "counts", "words")
+    return dict(zip(names, (int(v) for v in w)))
+
+
+def dof_partition(rows, D):
+    """(rows per step, slabs, rows per slab) of dhaug_dof_histogram: the documented function of (rows, D)"""
+    rg = DOF_BLOCK // D
+    steps = -(-rows // rg)
+    slabs = min(DOF_MAX_BLOCKS, -(-steps // DOF_MIN_STEPS))
+    per = -(-steps // slabs) if slabs else 0
+    slabs = -(-steps // per) if per else 0
+    return rg, slabs, per * rg
 
 
 def layernorm_workspace_doubles(C):

@@ -42,6 +42,14 @@ def forward_precision(p):
 
 
 class _GeneratorBase(nn.Module):
+    # utils.dof_stats.DofMonitor or None (the default: nothing is computed).  With one attached, forward and sample_for_critics
+    # hand the batch's (N, 37) angles to it whenever monitor.due(train_num) -- the reference's "first and every 500th call"
+    # (R/models_Fk_GAN/Fk_generator.py:172) -- from one extra tail launch without jitter under no_grad (the angles do not depend
+    # on the jitter): no random number is drawn, the returned poses and the device generator's offset are those of a run without
+    # a monitor.  While the stream is capturing NOTHING is fed: a replayed graph would count one batch over and over, and the
+    # call counter does not advance on replay.  gen_step.generator_step does not feed either.
+    dof_monitor = None
+
     def __init__(self, frames, FK_DH_Class, args, device, INPUT_VEC_DIM):
         super().__init__()
         self.video_frame_num = frames
@@ -112,6 +120,13 @@ class _GeneratorBase(nn.Module):
         g.set_offset(off + 8)
         return g.initial_seed(), off
 
+    def _feed_dof_monitor(self, head, bl):
+        m = self.dof_monitor
+        if m is None or not m.due(self.train_num) or not head.is_cuda or torch.cuda.is_current_stream_capturing():
+            return
+        with torch.no_grad():
+            m.feed(ops.gen_tail_forward(head.detach(), bl, None, bool(self.args.GAN_whether_use_preAngle), True)[1])
+
     def forward(self, input, bone_len_scaler=None):
         B, R = input.shape[0], self.video_frame_num
         head = self.trunk(input).reshape(B * R, 35)
@@ -132,10 +147,12 @@ class _GeneratorBase(nn.Module):
             fake = ops.gen_tail_forward_critics(head.contiguous(), bl, None, bool(self.args.GAN_whether_use_preAngle), None,
                                                 rng=(seed, off), want_critic_inputs=False)[0]
             self.train_num += 1
+            self._feed_dof_monitor(head, bl)
             return fake.reshape(B, 48)
         scaler = self._scaler(B, bone_len_scaler)
         fake = A.GenTailFn.apply(head.contiguous(), bl, scaler, bool(self.args.GAN_whether_use_preAngle))
         self.train_num += 1
+        self._feed_dof_monitor(head, bl)
         if self.record_angles:
             with torch.no_grad():
                 self.distribute_angle = [ops.gen_tail_forward(head.detach(), bl, scaler,
@@ -162,6 +179,7 @@ class Fk_Generator(_GeneratorBase):
                 raise RuntimeError("boneLength has %d rows, the batch needs %d (call GAN_generator_get_bone_length)"
                                    % (bl.shape[0], B))
             self.train_num += 1
+            self._feed_dof_monitor(head, bl)
             pre = bool(self.args.GAN_whether_use_preAngle)
             if (bone_len_scaler is None and self.args.bone_len_scaler == "different"
                     and not torch.cuda.is_current_stream_capturing()):

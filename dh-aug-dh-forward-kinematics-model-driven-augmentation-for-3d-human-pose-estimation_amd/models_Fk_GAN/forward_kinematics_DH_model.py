@@ -290,6 +290,31 @@ class Forward_Kinematics_DH_Model():
             i = ops.ik_fit_staged(first, *zip(*ops.IK_COARSE_TO_FINE), lo=lo, hi=hi).angles37
         return ops.ik_track(p, off, i, lo, hi, iters=iters, clamp_init=clamp_init)
 
+    def dof_distribution(self, poses, lengths=None, max_residual=1e-4, pairs=((0, 1),), into=None, **fit):
+        """The DOF angle distributions of a dataset (the reference ships their plots, my_draw_original_dataset_distribute_for_paper,
+        but not the solver behind them): fits the poses -- with `lengths`, or a list of sequences, by fit_sequences(cold_start=True,
+        **fit); otherwise by fit_pose(schedule="coarse_to_fine", **fit) -- and adds the 37 angles per pose to `into` (a
+        utils.dof_stats.DofDistribution; a new one with `pairs` when None), which is returned.  A pose whose residual is above
+        max_residual (1e-4 m: the README's converged pose) or NaN never enters the histogram; it is counted in `skipped`.
+        Nothing is read back: result() of the returned accumulator does that.
+
+        The angles of an IkFit are NOT unique -- several slots are redundant -- so this histogram describes THIS solver's
+        solutions, started as documented (T-pose, coarse to fine; a sequence's frames from the frame before), not the pose
+        manifold.  Slots that span +-180 degrees are binned linearly."""
+        from ..utils.dof_stats import DofDistribution
+        if into is not None and not isinstance(into, DofDistribution):
+            raise ValueError("dof_distribution: into must be a DofDistribution")
+        if into is not None and into.D != 37:
+            raise ValueError("dof_distribution: into must keep 37 slots, it keeps %d" % into.D)
+        if lengths is not None or isinstance(poses, (list, tuple)):
+            fitted = self.fit_sequences(poses, lengths, cold_start=True, **fit)
+        else:
+            fit.setdefault("schedule", "coarse_to_fine")
+            fitted = self.fit_pose(poses, **fit)
+        if into is None:
+            into = DofDistribution(37, pairs=pairs, device=fitted.angles37.device)
+        return into.add(fitted.angles37, fitted.residual, max_residual)
+
     def init_Fk_DH_angle(self):
         """T-pose with the default lengths (:824-858)."""
         z5, z13 = [0.0] * 5, [0.0] * 13

@@ -19,6 +19,7 @@ from .. import ops
 from ..common import camera as cam
 from ..common.h36m_dataset import h36m_cameras_extrinsic_params, h36m_cameras_intrinsic_params
 from ..optim import FusedAdam
+from ..utils import dof_stats
 from .Fk_discriminator import (Fk_2D_Discriminator, Fk_3D_Discriminator, Video_motion_Fk_2D_Discriminator,
                                Video_motion_Fk_3D_Discriminator, calc_gradient_penalty)
 from .Fk_generator import Fk_Generator, Video_Fk_Generator
@@ -46,12 +47,23 @@ def my_get_poseFk_model(args, dataset, FK_DH_Class):
     model_d3d = Fk_3D_Discriminator(device, args).to(device)
     model_d2d = Fk_2D_Discriminator(args, num_joints).to(device)
     lr = 1e-4                                    # lr_g / lr_d are parsed but ignored by the reference (:112)
-    return {
+    return _with_dof_monitor(args, device, {
         'model_G': model_G, 'model_d3d': model_d3d, 'model_d2d': model_d2d,
         'optimizer_G': FusedAdam(model_G.parameters(), lr=lr, betas=(0.5, 0.9)),
         'optimizer_d3d': FusedAdam(model_d3d.parameters(), lr=lr, betas=(0.5, 0.9)),
         'optimizer_d2d': FusedAdam(model_d2d.parameters(), lr=lr, betas=(0.5, 0.9)),
-    }
+    })
+
+
+def _with_dof_monitor(args, device, poseFk_dict):
+    """args.dof_monitor (or DHAUG_DOF_MONITOR=1; off by default, the argument parser does not know it): the generator feeds
+    its angle distributions -- 37 slots, its own limits, the paper's pair (8, 3) -- to poseFk_dict['dof_distribution'] on the
+    reference's schedule (utils/dof_stats.py)"""
+    if dof_stats.monitor_enabled(args):
+        monitor = dof_stats.generator_monitor(device=device)
+        poseFk_dict['model_G'].dof_monitor = monitor
+        poseFk_dict['dof_distribution'] = monitor.distribution
+    return poseFk_dict
 
 
 def video_mode_my_get_poseFk_model(args, dataset, FK_DH_Class, video_frame_num):
@@ -62,12 +74,12 @@ def video_mode_my_get_poseFk_model(args, dataset, FK_DH_Class, video_frame_num):
     model_motion_d3d = Video_motion_Fk_3D_Discriminator(device, args, video_frame_num).to(device)
     model_motion_d2d = Video_motion_Fk_2D_Discriminator(device, args, video_frame_num).to(device)
     mk = lambda m: FusedAdam(m.parameters(), lr=1e-4, betas=(0.5, 0.9))
-    return {
+    return _with_dof_monitor(args, device, {
         'model_G': model_G, 'model_d3d': model_d3d, 'model_d2d': model_d2d,
         'model_motion_d3d': model_motion_d3d, 'model_motion_d2d': model_motion_d2d,
         'optimizer_G': mk(model_G), 'optimizer_d3d': mk(model_d3d), 'optimizer_d2d': mk(model_d2d),
         'optimizer_motion_d3d': mk(model_motion_d3d), 'optimizer_motion_d2d': mk(model_motion_d2d),
-    }
+    })
 
 
 def traditional_solutions_FK_generator(args, FK_DH_Class, data_dict, train_subjects):

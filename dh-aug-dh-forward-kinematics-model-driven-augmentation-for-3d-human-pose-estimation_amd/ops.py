@@ -599,6 +599,118 @@ def pose_scaled_errors(pred, target, center=False, w=None, sums=None):
     return sums
 
 
+# ---------------------------------------------------------------------------------------------- DOF angle distributions
+def dof_record(D=37, device=None):
+    """a fresh record of dof_histogram for D slots: _lib.dof_record_offsets(D)['words'] int64 words (the fp64 fields are bit
+    patterns: view(torch.float64)), zeros with min = +inf and max = -inf"""
+    D = int(D)
+    if not 1 <= D <= _lib.DOF_MAX_SLOTS:
+        raise ValueError("dof_record: D must be in 1..%d, got %r" % (_lib.DOF_MAX_SLOTS, D))
+    off = _lib.dof_record_offsets(D)
+    rec = torch.zeros(off["words"], dtype=torch.int64, device=device if device is not None else "cuda")
+    f = rec.view(torch.float64)
+    f[off["min"]:off["min"] + D] = float("inf")
+    f[off["max"]:off["max"] + D] = float("-inf")
+    return rec
+
+
+def _dof_rows(angles, name):
+    """the angle table as fp32 (rows, D) with unit column stride (a row pitch >= D is passed on as it is: no copy)"""
+    if not torch.is_tensor(angles) or angles.dim() != 2:
+        raise ValueError("%s: angles must be a (rows, D) tensor, got %s"
+                         % (name, tuple(angles.shape) if torch.is_tensor(angles) else type(angles).__name__))
+    rows, D = angles.shape
+    if not 1 <= D <= _lib.DOF_MAX_SLOTS:
+        raise ValueError("%s: D must be in 1..%d, got %d" % (name, _lib.DOF_MAX_SLOTS, D))
+    a = angles if angles.dtype == torch.float32 else angles.float()
+    if rows > 1 and (a.stride(1) != 1 or a.stride(0) < D):
+        a = a.contiguous()
+    elif rows <= 1 and D > 1 and a.stride(1) != 1:
+        a = a.contiguous()
+    return a, rows, D, (a.stride(0) if rows > 1 else D)
+
+
+def _dof_residual(residual, max_residual, rows, name):
+    if residual is None:
+        if max_residual is not None:
+            raise ValueError("%s: max_residual goes with a residual" % name)
+        return None, 0.0
+    if max_residual is None:
+        raise ValueError("%s: a residual needs max_residual" % name)
+    if not torch.is_tensor(residual) or residual.numel() != rows:
+        raise ValueError("%s: residual must hold one value per row (%d)" % (name, rows))
+    r = residual.reshape(-1)
+    return (r if r.dtype == torch.float32 else r.float()).contiguous(), float(max_residual)
+
+
+def _dof_on_device(name, *tensors):
+    """every ValueError of a DOF entry comes before this check, so the refusals can be tested without a GPU"""
+    if any(t is not None and not t.is_cuda for t in tensors):
+        raise RuntimeError("dhaug op `%s` needs GPU tensors (no CPU fallback exists)" % name)
+
+
+def dof_histogram(angles, record, residual=None, max_residual=None, lo=None, hi=None, tol=0.0):
+    """record += the per-slot one-degree histograms (bin = int(angle) + 180 of 361), NaN / outside / at-limit counts, exact
+    min / max and fp64 sums of angles (rows, D) fp32 (dhaug_dof_histogram; a row-strided view is read in place).  record comes
+    from dof_record(D).  residual (rows) with max_residual: rows whose residual is larger, or NaN, are left out and counted in
+    `skipped`.  lo / hi: (D,) device tensors (both or neither) for at_lo += a <= fl32(lo + tol), at_hi += a >= fl32(hi - tol).
+    Enqueues two launches on the current stream; no host read.  ValueError before any launch for a bad argument."""
+    name = "dof_histogram"
+    a, rows, D, pitch = _dof_rows(angles, name)
+    words = _lib.dof_record_offsets(D)["words"]
+    if not (torch.is_tensor(record) and record.dtype == torch.int64 and record.numel() == words and record.is_contiguous()):
+        raise ValueError("%s: record must come from dof_record(%d) (%d int64 words)" % (name, D, words))
+    if (lo is None) != (hi is None):
+        raise ValueError("%s: lo and hi come together" % name)
+    if lo is not None:
+        if not (torch.is_tensor(lo) and torch.is_tensor(hi) and lo.numel() == D and hi.numel() == D):
+            raise ValueError("%s: lo and hi are tensors of %d entries each" % (name, D))
+        lo, hi = lo.reshape(-1).float().contiguous(), hi.reshape(-1).float().contiguous()
+    if not float(tol) >= 0.0:
+        raise ValueError("%s: tol must not be negative, got %r" % (name, tol))
+    res, mr = _dof_residual(residual, max_residual, rows, name)
+    _dof_on_device(name, a, record, res, lo, hi)
+    ws = torch.empty(_lib.DOF_WORKSPACE_BYTES // 8, dtype=torch.float64, device=a.device)
+    _lib.call("dhaug_dof_histogram", _p(a), rows, D, pitch, _p(res), mr, _p(lo), _p(hi), float(tol), _p(record), _p(ws), _stream())
+    return record
+
+
+def dof_pairs(pairs, D, name="dof_pair_histogram"):
+    """slot pairs as a list of (i, j) ints, checked as dhaug_dof_pair_histogram checks them"""
+    try:
+        out = [(int(i), int(j)) for i, j in pairs]
+    except (TypeError, ValueError):
+        raise ValueError("%s: pairs is a sequence of (i, j) slot pairs" % name)
+    if len(out) > _lib.DOF_MAX_PAIRS:
+        raise ValueError("%s: at most %d pairs per call, got %d" % (name, _lib.DOF_MAX_PAIRS, len(out)))
+    bad = [p for p in out if not (0 <= p[0] < D and 0 <= p[1] < D)]
+    if bad:
+        raise ValueError("%s: slot(s) outside [0, %d) in %s" % (name, D, bad))
+    return out
+
+
+def dof_pair_histogram(angles, pairs, table, residual=None, max_residual=None):
+    """table[p][bin(a_i)][bin(a_j)] += 1 over the rows of angles (rows, D) for the slot pairs p = (i, j), at most 4 per call
+    (dhaug_dof_pair_histogram).  table: int64 (len(pairs), 361, 361) on the device, accumulated into.  Same binning and skip
+    rule as dof_histogram; a row with a NaN in either slot of a pair is left out of that pair."""
+    name = "dof_pair_histogram"
+    a, rows, D, pitch = _dof_rows(angles, name)
+    pr = dof_pairs(pairs, D, name)
+    n = len(pr)
+    if not (torch.is_tensor(table) and table.dtype == torch.int64 and table.is_contiguous()
+            and tuple(table.shape) == (n, _lib.DOF_BINS, _lib.DOF_BINS)):
+        raise ValueError("%s: table must be a contiguous int64 tensor of shape (%d, %d, %d)"
+                         % (name, n, _lib.DOF_BINS, _lib.DOF_BINS))
+    res, mr = _dof_residual(residual, max_residual, rows, name)
+    _dof_on_device(name, a, table, res)
+    if n == 0:
+        return table
+    flat = [v for p in pr for v in p]
+    _lib.call("dhaug_dof_pair_histogram", _p(a), rows, D, pitch, _p(res), mr, (ctypes.c_int * (2 * n))(*flat), n, _p(table),
+              _stream())
+    return table
+
+
 def center_flip(x, center, flip, adjoint=False):
     C = x.shape[-1]
     v = _dev(x, torch.float32, "center_flip").reshape(-1, 16 * C)

@@ -1272,6 +1272,74 @@ int dhaug_ik_track(const float* pose16, const int64_t* seq_offset, const float* 
                    float* angles, float* bone_len, float* root, float* residual, int64_t S, int iters, float lambda0,
                    void* stream);
 
+/* ------------------------------------------------------------------------------------------------------
+ * DOF angle distributions (csrc/dhaug_dof.hip, per-value arithmetic in csrc/dhaug_dof_math.h): the tables that
+ * R/models_Fk_GAN/special_operate.py my_draw_DOF_angle_distribute :347-364 and my_draw_distribute_for_paper :420-442 build in
+ * Python loops, accumulated on the device.  angles: fp32 (rows, D) with `pitch` >= D floats between rows, 1 <= D <=
+ * DHAUG_DOF_MAX_SLOTS; D = 37 is generator_angle / IkFit.angles37, D = 33 the 'normal' sampler's table.
+ *
+ * Binning (both entries): bin = (int)truncf(a) + 180 of DHAUG_DOF_BINS = 361, the reference's int(angle) + 180: -0.5 -> 180 (bin
+ *   180 is two degrees wide), 180.5 -> 360 and -180.9 -> 0, both inside.  |truncf(a)| > 180 or +-inf: counted in the end bin 0 or
+ *   360 AND in `outside` (the reference wraps or raises there; this clamps and says so).  NaN: counted in `nan`, no bin.
+ * Skip rule (both entries): with `residual` (rows fp32, NULL = none) a row whose residual > max_residual, or is NaN, is left out
+ *   of everything and counted in `skipped`; residual == max_residual is kept.
+ *
+ * dhaug_dof_histogram accumulates into a caller-initialised record of DHAUG_DOF_RECORD_WORDS(D) 8-byte words:
+ *   word DHAUG_DOF_OFF_ROWS     int64   rows seen (skipped ones included)
+ *        DHAUG_DOF_OFF_SKIPPED  int64   rows left out by the skip rule
+ *        DHAUG_DOF_OFF_NAN(D) + d, _OUTSIDE, _AT_LO, _AT_HI, _INF   int64 per slot d (inf: the +-inf among `outside`, so
+ *                               that counts.sum() - inf is the number of values behind sum / sumsq)
+ *        DHAUG_DOF_OFF_MIN(D) + d, _MAX    fp64 per slot: the exact fp32 extreme of the non-NaN values (infinities included; of
+ *                               two zeros min keeps -0, max +0).  Initialise to +inf / -inf.
+ *        DHAUG_DOF_OFF_SUM(D) + d, _SUMSQ  fp64 per slot: sum of a and of a * a (exact products) over the FINITE values
+ *        DHAUG_DOF_OFF_COUNTS(D) + d * 361 + bin   int64
+ *   per slot counts.sum() + nan == rows - skipped.  at_lo += a <= fl32(lo[d] + tol), at_hi += a >= fl32(hi[d] - tol), compared in
+ *   fp32, with lo / hi (D each, device) both given or both NULL (then neither is counted).
+ *   Layout: a workgroup of DHAUG_DOF_BLOCK lanes walks a slab of consecutive rows downwards, RG = DHAUG_DOF_BLOCK / D whole rows
+ *   per step (lane l: slot l % D of row l / D of the step: one contiguous read), min / max / sum / sumsq in the lane's
+ *   registers, counts in an LDS table of D x 361 uint32 (no-return LDS adds).  The partition depends on (rows, D) only:
+ *   steps = ceil(rows / RG), slabs = min(DHAUG_DOF_MAX_BLOCKS, ceil(steps / DHAUG_DOF_MIN_STEPS)), steps per slab = ceil(steps /
+ *   slabs).  A slab's non-zero counters are added to the record with no-return global INTEGER adds -- they commute exactly, so
+ *   the counts are reproducible bits; the floating-point words never go through an atomic: every workgroup writes its four
+ *   values per slot to `workspace` (DHAUG_DOF_WORKSPACE_BYTES) and a one-workgroup second launch folds them into the record in
+ *   slab order.  The same call sequence gives the same bits in every word of the record.
+ * dhaug_dof_pair_histogram: table int64 (npairs, 361, 361), table[p][bin(a_i)][bin(a_j)] += 1 for the slot pairs (i, j) =
+ *   pairs[2 p], pairs[2 p + 1] (HOST ints, read before the call returns), npairs <= DHAUG_DOF_MAX_PAIRS.  A row with a NaN in
+ *   either slot of a pair is left out of that pair.  One lane per row, no-return global integer adds (a table does not fit
+ *   LDS); equal bins within a wave are not folded first.
+ * Both: DHAUG_EINVAL for rows < 0, D outside 1..64, a NULL record / workspace / table, (rows > 0) NULL angles, pitch < D, exactly
+ *   one of lo and hi, a pair index outside [0, D), npairs outside 0..4; DHAUG_EUNSUPPORTED for rows >= 2^31; DHAUG_EALIGN for a
+ *   record, workspace or table off the 8-byte grid.  All checked before any launch; rows = 0 (or npairs = 0) launches nothing.
+ *   No host read, no synchronisation; launches go to `stream` and can be captured.
+ * dhaug_dof_record_layout (host only): words13 (HOST) <- the first word of rows, skipped, nan, outside, at_lo, at_hi, inf, min,
+ *   max, sum, sumsq, counts and DHAUG_DOF_RECORD_WORDS(D), as THIS build of the library lays a record out: a binding checks its
+ *   own arithmetic against it.  DHAUG_EINVAL for D outside 1..64 or a NULL pointer. */
+#define DHAUG_DOF_BINS 361
+#define DHAUG_DOF_MAX_SLOTS 64
+#define DHAUG_DOF_MAX_PAIRS 4
+#define DHAUG_DOF_BLOCK 256             /* lanes of a workgroup: DHAUG_DOF_BLOCK / D rows per step */
+#define DHAUG_DOF_MAX_BLOCKS 512
+#define DHAUG_DOF_MIN_STEPS 16
+#define DHAUG_DOF_WORKSPACE_BYTES (DHAUG_DOF_MAX_BLOCKS * 4 * DHAUG_DOF_MAX_SLOTS * 8)
+#define DHAUG_DOF_OFF_ROWS 0
+#define DHAUG_DOF_OFF_SKIPPED 1
+#define DHAUG_DOF_OFF_NAN(D) 2
+#define DHAUG_DOF_OFF_OUTSIDE(D) (2 + (D))
+#define DHAUG_DOF_OFF_AT_LO(D) (2 + 2 * (D))
+#define DHAUG_DOF_OFF_AT_HI(D) (2 + 3 * (D))
+#define DHAUG_DOF_OFF_INF(D) (2 + 4 * (D))
+#define DHAUG_DOF_OFF_MIN(D) (2 + 5 * (D))
+#define DHAUG_DOF_OFF_MAX(D) (2 + 6 * (D))
+#define DHAUG_DOF_OFF_SUM(D) (2 + 7 * (D))
+#define DHAUG_DOF_OFF_SUMSQ(D) (2 + 8 * (D))
+#define DHAUG_DOF_OFF_COUNTS(D) (2 + 9 * (D))
+#define DHAUG_DOF_RECORD_WORDS(D) (2 + 9 * (D) + (D) * DHAUG_DOF_BINS)
+int dhaug_dof_record_layout(int64_t D, int64_t* words13);
+int dhaug_dof_histogram(const float* angles, int64_t rows, int64_t D, int64_t pitch, const float* residual, float max_residual,
+                        const float* lo, const float* hi, float tol, void* record, void* workspace, void* stream);
+int dhaug_dof_pair_histogram(const float* angles, int64_t rows, int64_t D, int64_t pitch, const float* residual,
+                             float max_residual, const int* pairs, int npairs, int64_t* table, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
